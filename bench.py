@@ -34,6 +34,13 @@ one rank (RCCL, world size 1), so the N=1 point runs the same code path as N=8.
 HIP training kernels -- the graphed single-model step at batch 1024 and 8192, 8 member-batched ensemble
 members, and the loss deviation of 10 HIP steps from the same steps on fp32 autograd.
 
+A plain run does only what the headline needs: set-up, W warmup steps, the K timed steps, the result
+line.  ``--full`` adds every other block described above and below (``extra.comm``, ``extra.fp32_deviation``,
+the other precision's engine, ``extra.train``, ``extra.fp32_paths``); without it those keys are ``null``.
+``--dump-outputs DIR`` writes what the last timed step computed (per-window probabilities and UQ metrics
+of both methods and the all-reduced aggregate sums) as ``DIR/<name>.npy``; inputs, weights and dropout
+masks depend only on the arguments, so two builds can be compared output for output.
+
 ``--device cpu`` is a dry run of the same launcher / collectives / metrics on gloo with the fp32
 reference model (CPU tests); its numbers are not performance claims.
 """
@@ -75,12 +82,19 @@ def parse(argv=None):
                     help="MC-Dropout BatchNorm of the headline: per-pass batch statistics over the whole window set "
                          "(the reference's model(x, training=True); default) or running statistics (standard MC "
                          "Dropout)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bf16 engine's timing (extra.bf16)")
-    ap.add_argument("--no-deviation", action="store_true", help="skip the fp32 deviation block")
-    ap.add_argument("--no-train", action="store_true", help="skip the training block (extra.train)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary blocks: metered collectives (extra.comm), fp32 "
+                         "deviation, the other precision's engine, training and the fp32 paths of the other "
+                         "architectures; off by default (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all; a fixed seeded sample of the windows when they would be larger)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the bf16 engine's timing (extra.bf16)")
+    ap.add_argument("--no-deviation", action="store_true", help="with --full: skip the fp32 deviation block")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training block (extra.train)")
     ap.add_argument("--deviation-windows", type=int, default=1024)
     ap.add_argument("--comm-steps", type=int, default=2,
-                    help="steps after the timed region with every collective metered (extra.comm; 0: off)")
+                    help="with --full: steps after the timed region with every collective metered (extra.comm; 0: off)")
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu = dry run of launcher + collectives on gloo with the fp32 reference model")
     return ap.parse_args(argv)
@@ -182,7 +196,8 @@ def run(a):
                 meter.step()
                 meter.phase("mcd")
             pm = engine.mcd(mode, x_loc, step_base + i)
-            s_mcd = pinf.aggregate_sums(uq_ops.metrics(pm), y_loc)
+            m_mcd = uq_ops.metrics(pm)
+            s_mcd = pinf.aggregate_sums(m_mcd, y_loc)
             if ev:
                 ev[1].record()
             t1 = time.perf_counter()
@@ -192,14 +207,16 @@ def run(a):
                 pd = pinf.all_to_all_members(engine.de(x_glob), world)
             else:
                 pd = engine.de(x_loc)
-            s_de = pinf.aggregate_sums(uq_ops.metrics(pd), y_loc)
+            m_de = uq_ops.metrics(pd)
+            s_de = pinf.aggregate_sums(m_de, y_loc)
             sums = torch.stack([s_mcd, s_de])
             if meter is not None:
                 meter.phase("aggregate")
             pdist.all_reduce_sum_(sums)
             if ev:
                 ev[2].record()
-            return sums, (t0, t1, time.perf_counter())
+            outs = {"mcd_probs": pm, "mcd_metrics": m_mcd, "de_probs": pd, "de_metrics": m_de, "aggregate_sums": sums}
+            return outs, (t0, t1, time.perf_counter())
 
         for i in range(warmup):
             step(i)
@@ -209,9 +226,10 @@ def run(a):
         if not cpu:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        sums = None
+        outs = None
         for i in range(steps):
-            sums, tt = step(warmup + i)
+            outs = None  # free the previous step's arrays first: every step allocates as the one before
+            outs, tt = step(warmup + i)
             if ev and steps <= 64:
                 torch.cuda.synchronize()  # per-step split of the two phases (events)
                 phase[0] += ev[0].elapsed_time(ev[1])
@@ -236,28 +254,35 @@ def run(a):
             comm_rec = meter.summary()
             comm_rec["note"] = "per step; metered on steps after the timed region; ms = HIP-event time on the compute stream"
             pdist.barrier()
-        return elapsed, sums, phase, comm_rec
+        return elapsed, outs, phase, comm_rec
 
     head_prec = "fp32" if cpu else a.precision
     engine = make(head_prec)
-    elapsed, sums, phase, comm_rec = timed(engine, a.bn_mode, a.steps, a.warmup, 0, comm_steps=a.comm_steps)
+    elapsed, outs, phase, comm_rec = timed(engine, a.bn_mode, a.steps, a.warmup, 0,
+                                           comm_steps=a.comm_steps if a.full else 0)
+    sums = outs["aggregate_sums"]
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, outs, rank, world, a.seed)
+    del outs
     agg_mcd = pinf.finalize_aggregates(sums[0])
     agg_de = pinf.finalize_aggregates(sums[1])
     ms = elapsed * 1e3 / a.steps
     value = n_glob * a.steps / elapsed
 
     deviation = None
-    if not cpu and not a.no_deviation:
+    if a.full and not cpu and not a.no_deviation:
         deviation = engine.deviation(x_glob[: a.deviation_windows], y_glob[: a.deviation_windows])
 
     secondary = None
-    if not cpu and not a.no_secondary:
+    if a.full and not cpu and not a.no_secondary:
         other = "bf16" if head_prec == "fp32" else "fp32"
         del engine
         torch.cuda.empty_cache()
         eng2 = make(other)
         k2 = max(1, min(a.steps, 10))
-        e2, s2, ph2, _ = timed(eng2, a.bn_mode, k2, 1, 10_000)
+        e2, o2, ph2, _ = timed(eng2, a.bn_mode, k2, 1, 10_000)
+        s2 = o2.pop("aggregate_sums")
+        del o2
         secondary = {
             "precision": other,
             "value": round(n_glob * k2 / e2, 1),
@@ -271,14 +296,14 @@ def run(a):
             secondary["fp32_deviation"] = eng2.deviation(x_glob[: a.deviation_windows], y_glob[: a.deviation_windows])
 
     train = None
-    if not cpu and not a.no_train:  # BASELINE.json config #2: the training step (every rank trains its own models)
+    if a.full and not cpu and not a.no_train:  # BASELINE.json config #2: the training step (every rank trains its own models)
         from bench import train_extra
 
         torch.cuda.empty_cache()
         train = train_extra.measure(dev, a.seed)
 
     fp32_paths = None
-    if not cpu and not a.no_train:  # the reference-precision paths of the other architectures + fp32 training
+    if a.full and not cpu and not a.no_train:  # the reference-precision paths of the other architectures + fp32 training
         # single-device numbers: rank 0 alone, between barriers (the other ranks wait), distributed=False
         from bench import fp32_micro
 
@@ -344,6 +369,35 @@ def run(a):
         }
         _emit(json.dumps(out))
     pdist.shutdown()
+
+
+DUMP_BUDGET = 64 << 20  # bytes, all files of all ranks of one --dump-outputs run
+
+
+def _dump_outputs(dirname, outs, rank, world, seed):
+    """Write one step's outputs as ``<name>.npy`` (``<name>.rank<r>.npy`` with more than one rank): the
+    (T, n) / (M, n) probabilities and (7, n) metrics of this rank's windows in float32, the all-reduced
+    (2, 9) aggregate sums in float64.  Over budget, every per-window array keeps the same seeded sample
+    of the windows, whose indices go to ``window_index`` (float64)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().to("cpu") for k, v in outs.items()}
+    arrays = {k: v.to(torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    per_window = [k for k in arrays if k != "aggregate_sums"]
+    n = arrays[per_window[0]].shape[-1]
+    budget = DUMP_BUDGET // world - arrays["aggregate_sums"].numel() * 8
+    col_bytes = sum(arrays[k].shape[0] * arrays[k].element_size() for k in per_window) + 8
+    if n * col_bytes > budget:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        idx = torch.randperm(n, generator=g)[: budget // col_bytes].sort().values
+        for k in per_window:
+            arrays[k] = arrays[k][..., idx]
+        arrays["window_index"] = idx.double()
+    suffix = "" if world == 1 else f".rank{rank}"
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), v.contiguous().numpy())
 
 
 def _mcd_deviation(R, spec, params, x32, y, T, seed, base, run_hip, uq_ops, pinf):

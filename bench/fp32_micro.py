@@ -1,6 +1,6 @@
 """Speed of the fp32 precision paths beside their bf16 counterparts.
 
-``python -m bench.fp32_micro``: one JSON line; ``measure()`` is also ``bench.py``'s ``extra.fp32_paths``.
+``python -m bench.fp32_micro``: one JSON line; ``measure()`` is also ``bench.py --full``'s ``extra.fp32_paths``.
 
 * inference of the pooled ensemble architecture (``/root/reference/models/train_deep_ensemble_cnns.py:36-66``
   MaxPool variant, loaded by ``evaluate_de_global.py:18-38``): Deep-Ensemble predict of 8 members and

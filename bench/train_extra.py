@@ -1,4 +1,4 @@
-"""Training throughput block of ``bench.py`` (``extra.train``): BASELINE.json config #2, "training (Adam,
+"""Training throughput block of ``bench.py --full`` (``extra.train``): BASELINE.json config #2, "training (Adam,
 BCE) on 1 x MI355X".
 
 The reference's training loop is Keras ``fit(batch_size=1024)`` with Adam and BCE

@@ -46,6 +46,60 @@ def test_bench_refuses_world_mismatch():
     assert "refusing" in r.stderr
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A run without ``--full`` meters no collectives, and ``--dump-outputs`` writes the last timed step's
+    arrays: float32 / float64, the shapes of T=3 passes, M=2 members, 7 metrics over 16 windows, the same
+    bytes from two runs with the same arguments, and aggregate sums that give the result line's figure."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--windows", "16", "--passes", "3", "--members", "2", "--steps", "2", "--warmup", "1"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    out = _bench(*args, "--dump-outputs", str(a))
+    _bench(*args, "--dump-outputs", str(b))
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert out["extra"]["comm"] is None and out["extra"]["fp32_deviation"] is None and out["extra"]["train"] is None
+    shapes = {"mcd_probs": (3, 16), "mcd_metrics": (7, 16), "de_probs": (2, 16), "de_metrics": (7, 16),
+              "aggregate_sums": (2, 9)}
+    assert sorted(os.listdir(a)) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        va, vb = np.load(a / (k + ".npy")), np.load(b / (k + ".npy"))
+        assert va.shape == shape and va.dtype in (np.float32, np.float64), (k, va.shape, va.dtype)
+        assert va.tobytes() == vb.tobytes(), k
+    s = np.load(a / "aggregate_sums.npy")
+    assert s[0, 0] == 16 and abs(s[0, 6] / 16 - out["extra"]["mcd_mean_entropy"]) < 1e-6
+
+
+def test_bench_dump_samples_windows_over_budget(tmp_path):
+    """Over the byte budget every per-window array keeps the same seeded sample of the windows."""
+    import numpy as np
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_script", os.path.join(ROOT, "bench.py"))  # bench/ is a package
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    outs ={"mcd_probs": torch.rand(3, 40), "mcd_metrics": torch.rand(7, 40), "de_probs": torch.rand(2, 40),
+            "de_metrics": torch.rand(7, 40), "aggregate_sums": torch.rand(2, 9, dtype=torch.float64)}
+    old = bench.DUMP_BUDGET
+    bench.DUMP_BUDGET = 2 * 9 * 8 + 10 * ((3 + 7 + 2 + 7) * 4 + 8)  # room for 10 of the 40 windows
+    try:
+        bench._dump_outputs(str(tmp_path), outs, 0, 1, seed=5)
+        bench._dump_outputs(str(tmp_path / "again"), outs, 0, 1, seed=5)
+    finally:
+        bench.DUMP_BUDGET = old
+    idx = np.load(tmp_path / "window_index.npy")
+    assert idx.shape == (10,) and len(set(idx.tolist())) == 10 and (np.diff(idx) > 0).all()
+    assert (idx == np.load(tmp_path / "again" / "window_index.npy")).all()
+    total = 0
+    for k, v in outs.items():
+        got = np.load(tmp_path / (k + ".npy"))
+        total += got.nbytes
+        want = v.numpy() if k == "aggregate_sums" else v.numpy()[:, idx.astype(np.int64)]
+        assert (got == want).all(), k
+    assert total + idx.nbytes <= 2 * 9 * 8 + 10 * ((3 + 7 + 2 + 7) * 4 + 8)
+
+
 @pytest.mark.parametrize("n", [1, 3])
 def test_launch_spawn_exit_codes(n, tmp_path):
     from uncertaintyquantification_sleepapnea_1dcnn_amd.parallel import launch
@@ -65,7 +119,7 @@ def test_bench_comm_block_counts_collectives():
     row count (6 layers x 2 x T); Deep Ensemble = one all_to_all of the member probabilities; then one
     all-reduce of the 2 x 9 fp64 aggregate sums."""
     out = _bench("--gpus", "2", "--windows", "24", "--passes", "3", "--members", "2", "--steps", "1", "--warmup", "1",
-                 "--no-secondary", "--comm-steps", "2")
+                 "--full", "--no-secondary", "--comm-steps", "2")
     c = out["extra"]["comm"]
     assert c["steps"] == 2
     ph = c["phases"]

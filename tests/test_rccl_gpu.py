@@ -34,7 +34,7 @@ def test_rccl_world1_collectives():
 
 def test_bench_reports_rccl_world1():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--windows", "512", "--passes",
-                        "4", "--steps", "2", "--warmup", "1", "--no-deviation"],
+                        "4", "--steps", "2", "--warmup", "1", "--full", "--no-deviation"],
                        capture_output=True, text=True, timeout=240, env=_clean_env(APNEAUQ_FORCE_PG="1"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
