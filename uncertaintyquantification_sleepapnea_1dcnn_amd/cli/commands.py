@@ -22,6 +22,7 @@
 | convergence_sweep | (new) computes the convergence CSV the reference produced by hand |
 | shhs_cohort_analysis / shhs_signal_quality | datasets/SHHS_cohort_analysis.py / SHHS_signal_quality.py |
 | uq_demo | uq_techniques.py ``__main__`` demo |
+| analyze_calibration | (new) calibration + selective prediction with bootstrap CIs from a detail CSV |
 """
 from __future__ import annotations
 
@@ -297,6 +298,40 @@ def shhs_signal_quality(argv=None):
     from ..data.cohort import main_quality
 
     main_quality(argv)
+
+
+def analyze_calibration(argv=None):
+    ap = argparse.ArgumentParser(description="Calibration (ECE/MCE/Brier/NLL) and selective prediction "
+                                             "(accuracy vs coverage) of a per-window detail CSV, with bootstrap CIs.")
+    ap.add_argument("--input_csv", type=str, default="./detail_patient_DE.csv")
+    ap.add_argument("--score", choices=["Predictive_Entropy", "Predictive_Variance"], default="Predictive_Entropy",
+                    help="uncertainty column by which windows are referred")
+    ap.add_argument("--n_bins", type=int, default=15)
+    ap.add_argument("--n_bootstrap", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--output_plot_dir", type=str, default="./uq_plots/calibration")
+    ap.add_argument("--output_csv", type=str, default="./calibration_metrics.csv")
+    ap.add_argument("--no_plots", action="store_true")
+    a = ap.parse_args(argv)
+    import pandas as pd
+
+    from ..uq.calibration import evaluate_calibration
+
+    df = pd.read_csv(a.input_csv)
+    label = os.path.splitext(os.path.basename(a.input_csv))[0]
+    res = evaluate_calibration(df["Predicted_Probability"].to_numpy(np.float32), df["True_Label"].to_numpy(), label,
+                               n_bootstrap=a.n_bootstrap, random_state=a.seed,
+                               score=df[a.score].to_numpy(np.float32), n_bins=a.n_bins,
+                               output_plot_dir=a.output_plot_dir, make_plots=not a.no_plots)
+    ends = ("_mean", "_ci_lower", "_ci_upper")
+    rows = [{"metric": k, "value": v, "mean": res.get(k + "_mean", np.nan), "ci_lower": res.get(k + "_ci_lower", np.nan),
+             "ci_upper": res.get(k + "_ci_upper", np.nan)} for k, v in res.items() if not k.endswith(ends)]
+    table = pd.DataFrame(rows, columns=["metric", "value", "mean", "ci_lower", "ci_upper"])
+    print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
+    if a.output_csv:
+        os.makedirs(os.path.dirname(os.path.abspath(a.output_csv)), exist_ok=True)
+        table.to_csv(a.output_csv, index=False)
+    return table
 
 
 def uq_demo(argv=None):

@@ -33,6 +33,10 @@ hipError_t launch_bootstrap(const float* metrics, const int* y, const int* idx, 
                             double* out, hipStream_t stream);
 hipError_t launch_bootstrap_partial(const float* metrics, const int* y, const int* idx, unsigned seed, int n, int lo,
                                     int n_loc, int n_boot, double* out, hipStream_t stream);
+hipError_t launch_calib_prep(const float* p, const float* score, const int* y, const float* thr, int n, int n_bins,
+                             int n_thr, int* rec, hipStream_t stream);
+hipError_t launch_calib_bootstrap(const int* rec, const int* idx, unsigned seed, int n, int lo, int n_loc, int n_boot,
+                                  int n_bins, int n_thr, int slices, long long* out, hipStream_t stream);
 int zero_max_buffers();
 hipError_t launch_zero(int nb, void* const* ptrs, const long long* words, hipStream_t stream);
 int adam_max_sets();
@@ -299,6 +303,61 @@ at::Tensor bootstrap_partial(const at::Tensor& metrics, const at::Tensor& y, con
                                           (int)lo, (int)n_loc, (int)n_boot, out.data_ptr<double>(), cur_stream()),
         "bootstrap_partial");
   return out;
+}
+
+// Calibration / selective prediction (uq_calib.hip): per-window integer records, then the bootstrap
+// histogram sums.  Limits: K <= 32 bins, J <= 64 thresholds, n <= 2^27 (sum nll_q stays below 2^63).
+at::Tensor calib_prep(const at::Tensor& p, const at::Tensor& score, const at::Tensor& y, const at::Tensor& thr,
+                      int64_t n_bins) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.dim() == 1, "calib_prep: p must be (N,) float32 on the GPU");
+  const int64_t n = p.size(0), n_thr = thr.numel();
+  TORCH_CHECK(score.is_cuda() && score.scalar_type() == at::kFloat && score.dim() == 1 && score.size(0) == n,
+              "calib_prep: score must be (N,) float32 on the GPU");
+  TORCH_CHECK(thr.is_cuda() && thr.scalar_type() == at::kFloat && thr.dim() == 1,
+              "calib_prep: thr must be (J,) float32 on the GPU");
+  TORCH_CHECK(n_bins >= 1 && n_bins <= 32, "calib_prep: n_bins must be in 1..32");
+  TORCH_CHECK(n_thr <= 64, "calib_prep: at most 64 thresholds");
+  TORCH_CHECK(n <= (int64_t(1) << 27), "calib_prep: at most 2^27 windows");
+  auto pp = p.contiguous(), ss = score.contiguous(), tt = thr.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.dim() == 1 && yy.size(0) == n, "calib_prep: y must be (N,) on the GPU");
+  const at::DeviceGuard guard(pp.device());
+  auto rec = at::empty({n, 4}, pp.options().dtype(at::kInt));
+  check(apneauq::launch_calib_prep(pp.data_ptr<float>(), ss.data_ptr<float>(), yy.data_ptr<int>(), tt.data_ptr<float>(),
+                                   (int)n, (int)n_bins, (int)n_thr, rec.data_ptr<int>(), cur_stream()),
+        "calib_prep");
+  return rec;
+}
+
+at::Tensor calib_bootstrap(const at::Tensor& rec, const c10::optional<at::Tensor>& idx, int64_t seed, int64_t n_boot,
+                           int64_t n_global, int64_t lo, int64_t n_bins, int64_t n_thr, int64_t slices) {
+  TORCH_CHECK(rec.is_cuda() && rec.scalar_type() == at::kInt && rec.dim() == 2 && rec.size(1) == 4,
+              "calib_bootstrap: rec must be the (n_loc, 4) int32 output of calib_prep");
+  const int64_t n_loc = rec.size(0);
+  TORCH_CHECK(n_bins >= 1 && n_bins <= 32, "calib_bootstrap: n_bins must be in 1..32");
+  TORCH_CHECK(n_thr >= 0 && n_thr <= 64, "calib_bootstrap: n_thr must be in 0..64");
+  TORCH_CHECK(n_global >= 1 && n_global <= (int64_t(1) << 27), "calib_bootstrap: n_global must be in 1..2^27");
+  TORCH_CHECK(lo >= 0 && lo + n_loc <= n_global, "calib_bootstrap: bad shard");
+  TORCH_CHECK(n_boot >= 0 && n_boot < (int64_t(1) << 31), "calib_bootstrap: bad n_boot");
+  TORCH_CHECK(slices >= 1 && slices <= 1024, "calib_bootstrap: slices must be in 1..1024");
+  auto rr = rec.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rr.data_ptr()) % 16 == 0, "calib_bootstrap: 16-B alignment required");
+  const int* ip = nullptr;
+  at::Tensor ii;
+  if (idx.has_value()) {
+    ii = idx->to(at::kInt).contiguous();
+    TORCH_CHECK(ii.is_cuda() && ii.dim() == 2 && ii.size(0) == n_boot && ii.size(1) == n_global,
+                "calib_bootstrap: idx must be (B, n_global) on the GPU");
+    ip = ii.data_ptr<int>();
+  }
+  const int64_t n_col = 3 * n_bins + 4 * (n_thr + 1) + 2;
+  const at::DeviceGuard guard(rr.device());
+  auto slabs = at::empty({n_boot, slices, n_col}, rr.options().dtype(at::kLong));
+  check(apneauq::launch_calib_bootstrap(rr.data_ptr<int>(), ip, (unsigned)seed, (int)n_global, (int)lo, (int)n_loc,
+                                        (int)n_boot, (int)n_bins, (int)n_thr, (int)slices,
+                                        reinterpret_cast<long long*>(slabs.data_ptr<int64_t>()), cur_stream()),
+        "calib_bootstrap");
+  return slices == 1 ? slabs.select(1, 0) : slabs.sum(1);
 }
 
 void adam_step(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Tensor& v, double b1, double b2, double alpha,
@@ -1174,6 +1233,8 @@ TORCH_LIBRARY(apneauq, m) {
   m.def("uq_reduce(Tensor probs) -> Tensor");
   m.def("bootstrap(Tensor metrics, Tensor y, Tensor? idx, int seed, int n_boot) -> Tensor");
   m.def("bootstrap_partial(Tensor metrics, Tensor y, Tensor? idx, int seed, int n_boot, int n_global, int lo) -> Tensor");
+  m.def("calib_prep(Tensor p, Tensor score, Tensor y, Tensor thr, int n_bins) -> Tensor");
+  m.def("calib_bootstrap(Tensor rec, Tensor? idx, int seed, int n_boot, int n_global, int lo, int n_bins, int n_thr, int slices) -> Tensor");
   m.def("fused_layout() -> int[]", &fused_layout);
   m.def("fused_layout_x3() -> int[]", &fused_layout_x3);
   m.def("fused_tiled_x3_forward(Tensor x, Tensor blob, int net, int n_pass, int window_offset, int pass_offset, "
@@ -1235,6 +1296,8 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("uq_reduce", &uq_reduce);
   m.impl("bootstrap", &bootstrap);
   m.impl("bootstrap_partial", &bootstrap_partial);
+  m.impl("calib_prep", &calib_prep);
+  m.impl("calib_bootstrap", &calib_bootstrap);
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_multi", &adam_step_multi);
   m.impl("bump_counters", &bump_counters);
