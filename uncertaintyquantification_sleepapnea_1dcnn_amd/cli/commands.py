@@ -23,6 +23,7 @@
 | shhs_cohort_analysis / shhs_signal_quality | datasets/SHHS_cohort_analysis.py / SHHS_signal_quality.py |
 | uq_demo | uq_techniques.py ``__main__`` demo |
 | analyze_calibration | (new) calibration + selective prediction with bootstrap CIs from a detail CSV |
+| analyze_patient_severity | (new) per-patient apnea index, severity and cohort metrics with patient-cluster bootstrap CIs |
 """
 from __future__ import annotations
 
@@ -331,6 +332,47 @@ def analyze_calibration(argv=None):
     if a.output_csv:
         os.makedirs(os.path.dirname(os.path.abspath(a.output_csv)), exist_ok=True)
         table.to_csv(a.output_csv, index=False)
+    return table
+
+
+def analyze_patient_severity(argv=None):
+    ap = argparse.ArgumentParser(description="Per-patient window apnea index and severity with uncertainty, and cohort "
+                                             "metrics with patient-cluster bootstrap CIs, from a per-window detail CSV.")
+    ap.add_argument("--input_csv", type=str, default="./detailed_results_MCD.csv",
+                    help="per-window CSV with Patient_ID, True_Label and Predicted_Probability")
+    ap.add_argument("--raw_pred", type=str, default=None,
+                    help="(T, N, 1) .npy dump of the passes (mc_raw_pred*.npy); without it the mean prediction is the "
+                         "only pass")
+    ap.add_argument("--window_seconds", type=float, default=60.0)
+    ap.add_argument("--n_bootstrap", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--no_parity", action="store_true", help="draw patients with the device counter hash")
+    ap.add_argument("--output_dir", type=str, default="./uq_plots/patient_severity")
+    ap.add_argument("--no_plots", action="store_true")
+    a = ap.parse_args(argv)
+    import pandas as pd
+
+    from ..uq.patient_level import COHORT_KEYS, evaluate_patient_level
+
+    df = pd.read_csv(a.input_csv)
+    label = os.path.splitext(os.path.basename(a.input_csv))[0]
+    if a.raw_pred:
+        pred = np.load(a.raw_pred).astype(np.float32)
+        n = pred.shape[1] if pred.ndim >= 2 else pred.shape[0]
+        if n != len(df):
+            raise ValueError(f"{a.raw_pred} holds {n} windows, {a.input_csv} {len(df)}")
+    else:
+        pred = df["Predicted_Probability"].to_numpy(np.float32)
+        print("No --raw_pred: one pass (the mean prediction); the credible intervals are points (num_passes = 1).")
+    res = evaluate_patient_level(pred, df["True_Label"].to_numpy(), df["Patient_ID"].to_numpy(), label,
+                                 n_bootstrap=a.n_bootstrap, random_state=a.seed, parity=not a.no_parity,
+                                 output_dir=a.output_dir, make_plots=not a.no_plots, window_seconds=a.window_seconds)
+    rows = [{"metric": k, "value": res[k], "ci_lower": res.get(k + "_ci_lower", np.nan),
+             "ci_upper": res.get(k + "_ci_upper", np.nan)} for k in COHORT_KEYS]
+    table = pd.DataFrame(rows, columns=["metric", "value", "ci_lower", "ci_upper"])
+    print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
+    table.to_csv(os.path.join(a.output_dir, f"patient_cohort_metrics_{label}.csv"), index=False)
+    print(f"Saved patient table to: {os.path.join(a.output_dir, f'patient_severity_{label}.csv')}")
     return table
 
 

@@ -7,7 +7,9 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstdint>
 #include <cstring>
+#include <tuple>
 #include <vector>
 
 namespace apneauq {
@@ -37,6 +39,10 @@ hipError_t launch_calib_prep(const float* p, const float* score, const int* y, c
                              int n_thr, int* rec, hipStream_t stream);
 hipError_t launch_calib_bootstrap(const int* rec, const int* idx, unsigned seed, int n, int lo, int n_loc, int n_boot,
                                   int n_bins, int n_thr, int slices, long long* out, hipStream_t stream);
+hipError_t launch_patient_reduce(const float* probs, const float* m, const int* y, const int* code, int t_count, int n,
+                                 int n_pat, int* pass_pos, long long* rec, hipStream_t stream);
+hipError_t launch_patient_bootstrap(const long long* prec, const int* idx, unsigned seed, int n_pat, int n_boot,
+                                    long long* out, hipStream_t stream);
 int zero_max_buffers();
 hipError_t launch_zero(int nb, void* const* ptrs, const long long* words, hipStream_t stream);
 int adam_max_sets();
@@ -358,6 +364,64 @@ at::Tensor calib_bootstrap(const at::Tensor& rec, const c10::optional<at::Tensor
                                         reinterpret_cast<long long*>(slabs.data_ptr<int64_t>()), cur_stream()),
         "calib_bootstrap");
   return slices == 1 ? slabs.select(1, 0) : slabs.sum(1);
+}
+
+// Patient-level sums (uq_patient.hip).  Limits: n <= 2^27 windows (a fixed-point term is at most 2^32, so every
+// rec sum stays below 2^59), T <= 65536, P <= 2^24 and T P < 2^31.  Windows with a code outside [0, P) are skipped.
+std::tuple<at::Tensor, at::Tensor> patient_reduce(const at::Tensor& probs, const at::Tensor& m, const at::Tensor& y,
+                                                  const at::Tensor& code, int64_t n_pat) {
+  TORCH_CHECK(probs.is_cuda() && probs.scalar_type() == at::kFloat && probs.dim() == 2,
+              "patient_reduce: probs must be a (T, n) float32 GPU tensor");
+  const int64_t t_count = probs.size(0), n = probs.size(1);
+  TORCH_CHECK(m.is_cuda() && m.scalar_type() == at::kFloat && m.dim() == 2 && m.size(0) == 7 && m.size(1) == n,
+              "patient_reduce: m must be the (7, n) output of uq_reduce");
+  TORCH_CHECK(t_count >= 1 && t_count <= 65536, "patient_reduce: T must be in 1..65536");
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 27), "patient_reduce: n must be in 1..2^27");
+  TORCH_CHECK(n_pat >= 1 && n_pat <= (int64_t(1) << 24) && t_count * n_pat < (int64_t(1) << 31),
+              "patient_reduce: P must be in 1..2^24 with T P < 2^31");
+  TORCH_CHECK(code.is_cuda() && code.scalar_type() == at::kInt && code.dim() == 1 && code.size(0) == n,
+              "patient_reduce: code must be (n,) int32 on the GPU");
+  auto pp = probs.contiguous(), mm = m.contiguous(), cc = code.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.dim() == 1 && yy.size(0) == n, "patient_reduce: y must be (n,) on the GPU");
+  const at::DeviceGuard guard(pp.device());
+  auto pass_pos = at::zeros({t_count, n_pat}, pp.options().dtype(at::kInt));
+  auto rec = at::zeros({n_pat, 12}, pp.options().dtype(at::kLong));
+  check(apneauq::launch_patient_reduce(pp.data_ptr<float>(), mm.data_ptr<float>(), yy.data_ptr<int>(),
+                                       cc.data_ptr<int>(), (int)t_count, (int)n, (int)n_pat, pass_pos.data_ptr<int>(),
+                                       reinterpret_cast<long long*>(rec.data_ptr<int64_t>()), cur_stream()),
+        "patient_reduce");
+  return {pass_pos, rec};
+}
+
+// Patient-cluster bootstrap: (B, 41) sums of the (P, 25) per-patient records over P draws per replicate.
+// Limits: P <= 2^20 and P max|prec| < 2^63, so that no replicate (which may draw one patient P times) overflows.
+at::Tensor patient_bootstrap(const at::Tensor& prec, const c10::optional<at::Tensor>& idx, int64_t seed,
+                             int64_t n_boot) {
+  TORCH_CHECK(prec.is_cuda() && prec.scalar_type() == at::kLong && prec.dim() == 2 && prec.size(1) == 25,
+              "patient_bootstrap: prec must be a (P, 25) int64 GPU tensor");
+  const int64_t n_pat = prec.size(0);
+  TORCH_CHECK(n_pat >= 1 && n_pat <= (int64_t(1) << 20), "patient_bootstrap: P must be in 1..2^20");
+  TORCH_CHECK(n_boot >= 0 && n_boot < (int64_t(1) << 31), "patient_bootstrap: bad n_boot");
+  auto rr = prec.contiguous();
+  const int64_t lo = rr.min().item<int64_t>(), hi = rr.max().item<int64_t>();
+  const int64_t lim = INT64_MAX / n_pat;
+  TORCH_CHECK(lo >= -lim && hi <= lim, "patient_bootstrap: P max|prec| must stay below 2^63");
+  const int* ip = nullptr;
+  at::Tensor ii;
+  if (idx.has_value()) {
+    ii = idx->to(at::kInt).contiguous();
+    TORCH_CHECK(ii.is_cuda() && ii.dim() == 2 && ii.size(0) == n_boot && ii.size(1) == n_pat,
+                "patient_bootstrap: idx must be (B, P) on the GPU");
+    ip = ii.data_ptr<int>();
+  }
+  const at::DeviceGuard guard(rr.device());
+  auto out = at::empty({n_boot, 41}, rr.options());
+  check(apneauq::launch_patient_bootstrap(reinterpret_cast<const long long*>(rr.data_ptr<int64_t>()), ip, (unsigned)seed,
+                                          (int)n_pat, (int)n_boot, reinterpret_cast<long long*>(out.data_ptr<int64_t>()),
+                                          cur_stream()),
+        "patient_bootstrap");
+  return out;
 }
 
 void adam_step(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Tensor& v, double b1, double b2, double alpha,
@@ -1235,6 +1299,8 @@ TORCH_LIBRARY(apneauq, m) {
   m.def("bootstrap_partial(Tensor metrics, Tensor y, Tensor? idx, int seed, int n_boot, int n_global, int lo) -> Tensor");
   m.def("calib_prep(Tensor p, Tensor score, Tensor y, Tensor thr, int n_bins) -> Tensor");
   m.def("calib_bootstrap(Tensor rec, Tensor? idx, int seed, int n_boot, int n_global, int lo, int n_bins, int n_thr, int slices) -> Tensor");
+  m.def("patient_reduce(Tensor probs, Tensor m, Tensor y, Tensor code, int n_pat) -> (Tensor, Tensor)");
+  m.def("patient_bootstrap(Tensor prec, Tensor? idx, int seed, int n_boot) -> Tensor");
   m.def("fused_layout() -> int[]", &fused_layout);
   m.def("fused_layout_x3() -> int[]", &fused_layout_x3);
   m.def("fused_tiled_x3_forward(Tensor x, Tensor blob, int net, int n_pass, int window_offset, int pass_offset, "
@@ -1298,6 +1364,8 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("bootstrap_partial", &bootstrap_partial);
   m.impl("calib_prep", &calib_prep);
   m.impl("calib_bootstrap", &calib_bootstrap);
+  m.impl("patient_reduce", &patient_reduce);
+  m.impl("patient_bootstrap", &patient_bootstrap);
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_multi", &adam_step_multi);
   m.impl("bump_counters", &bump_counters);
