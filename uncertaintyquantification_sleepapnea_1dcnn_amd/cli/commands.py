@@ -24,6 +24,7 @@
 | uq_demo | uq_techniques.py ``__main__`` demo |
 | analyze_calibration | (new) calibration + selective prediction with bootstrap CIs from a detail CSV |
 | analyze_patient_severity | (new) per-patient apnea index, severity and cohort metrics with patient-cluster bootstrap CIs |
+| analyze_pass_convergence | (new) how many passes / members are enough: every metric against the count, with bands over random subsets, from one raw prediction dump |
 """
 from __future__ import annotations
 
@@ -373,6 +374,57 @@ def analyze_patient_severity(argv=None):
     print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
     table.to_csv(os.path.join(a.output_dir, f"patient_cohort_metrics_{label}.csv"), index=False)
     print(f"Saved patient table to: {os.path.join(a.output_dir, f'patient_severity_{label}.csv')}")
+    return table
+
+
+def analyze_pass_convergence(argv=None):
+    ap = argparse.ArgumentParser(description="Convergence of the uncertainty metrics with the number of MC-Dropout passes "
+                                             "or ensemble members, from one raw prediction dump: the value of the order "
+                                             "as run and the band over random subsets at every count.")
+    ap.add_argument("--input_csv", type=str, default="./detailed_results_MCD.csv",
+                    help="per-window detail CSV, read for True_Label")
+    ap.add_argument("--raw_pred", type=str, default="./mc_raw_pred0205.npy",
+                    help="(T, N[, 1]) .npy dump of the passes / members (mc_raw_pred*.npy)")
+    ap.add_argument("--balanced_csv", type=str, default=None, help="detail CSV of the balanced set (optional)")
+    ap.add_argument("--balanced_raw_pred", type=str, default=None, help="raw dump of the balanced set (optional)")
+    ap.add_argument("--counts", type=str, default=None, help="comma-separated counts (default 1,2,3,5,10,15,20,30,...,T)")
+    ap.add_argument("--n_orders", type=int, default=100, help="random orders of the passes behind the bands")
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--tolerance", type=float, default=0.05, help="relative distance to the all-T value that counts as converged")
+    ap.add_argument("--method", type=str, default="mcd", choices=["mcd", "de"])
+    ap.add_argument("--output_dir", type=str, default="./uq_plots/convergence")
+    ap.add_argument("--no_plots", action="store_true")
+    a = ap.parse_args(argv)
+    import pandas as pd
+
+    from ..uq import convergence as CV
+    from ..uq.drivers import convergence_from_predictions
+
+    def load(csv, raw):
+        df = pd.read_csv(csv)
+        pred = np.load(raw).astype(np.float32)
+        n = pred.shape[1] if pred.ndim >= 2 else pred.shape[0]
+        if n != len(df):
+            raise ValueError(f"{raw} holds {n} windows, {csv} {len(df)}")
+        return CV.on_device(pred), df["True_Label"].to_numpy()
+
+    if bool(a.balanced_csv) != bool(a.balanced_raw_pred):
+        raise ValueError("--balanced_csv and --balanced_raw_pred go together")
+    counts = [int(c) for c in a.counts.split(",")] if a.counts else None
+    label = f"{a.method}_{os.path.splitext(os.path.basename(a.input_csv))[0]}"
+    pu, yu = load(a.input_csv, a.raw_pred)
+    pb, yb = load(a.balanced_csv, a.balanced_raw_pred) if a.balanced_csv else (None, None)
+    res = CV.evaluate_convergence(pu, yu, label, counts=counts, n_orders=a.n_orders, random_state=a.seed,
+                                  tolerance=a.tolerance, output_dir=a.output_dir, make_plots=not a.no_plots)
+    unit = "passes" if a.method == "mcd" else "members"
+    table = pd.DataFrame([{"metric": m, f"{unit}_needed": res[f"passes_needed_{m}"]} for m in CV.METRICS])
+    print(f"{pu.shape[0]} {unit}, {pu.shape[1]} windows; tolerance {a.tolerance:g} of the all-{pu.shape[0]} value "
+          f"(flip_rate: at most 0.01 of the windows)")
+    print(table.to_string(index=False))
+    table.to_csv(os.path.join(a.output_dir, f"passes_needed_{label}.csv"), index=False)
+    out_csv = os.path.join(a.output_dir, f"convergence_{a.method}.csv")
+    convergence_from_predictions(pu, yu, pb, yb, counts, out_csv, n_orders=a.n_orders, seed=a.seed)
+    print(f"Saved the curves to: {os.path.join(a.output_dir, f'convergence_{label}.csv')} and {out_csv}")
     return table
 
 

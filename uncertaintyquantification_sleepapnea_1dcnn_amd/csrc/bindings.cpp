@@ -43,6 +43,8 @@ hipError_t launch_patient_reduce(const float* probs, const float* m, const int* 
                                  int n_pat, int* pass_pos, long long* rec, hipStream_t stream);
 hipError_t launch_patient_bootstrap(const long long* prec, const int* idx, unsigned seed, int n_pat, int n_boot,
                                     long long* out, hipStream_t stream);
+hipError_t launch_converge(const float* probs, const int* y, const int* orders, const int* counts, int t_count, int n,
+                           int n_rep, int n_cnt, int rep_groups, long long* out, hipStream_t stream);
 int zero_max_buffers();
 hipError_t launch_zero(int nb, void* const* ptrs, const long long* words, hipStream_t stream);
 int adam_max_sets();
@@ -421,6 +423,38 @@ at::Tensor patient_bootstrap(const at::Tensor& prec, const c10::optional<at::Ten
                                           (int)n_pat, (int)n_boot, reinterpret_cast<long long*>(out.data_ptr<int64_t>()),
                                           cur_stream()),
         "patient_bootstrap");
+  return out;
+}
+
+// Pass / member-count convergence (uq_converge.hip): (R, K, 11) int64 sums over the windows of the metrics of
+// the first counts[k] passes of orders[r].  Limits: T <= 128 (the tile's planes fit LDS), K <= 32, R <= 4096 and
+// n <= 2^22 per launch (a fixed-point term is at most 2^40, so every sum stays below 2^62; the front end splits
+// larger sets and adds).  The kernel clamps the pass indices to [0, T); ops/converge.py checks orders and counts.
+at::Tensor converge(const at::Tensor& probs, const at::Tensor& y, const at::Tensor& orders, const at::Tensor& counts,
+                    int64_t rep_groups) {
+  TORCH_CHECK(probs.is_cuda() && probs.scalar_type() == at::kFloat && probs.dim() == 2,
+              "converge: probs must be a (T, n) float32 GPU tensor");
+  const int64_t t_count = probs.size(0), n = probs.size(1);
+  TORCH_CHECK(t_count >= 1 && t_count <= 128, "converge: T must be in 1..128");
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 22), "converge: n must be in 1..2^22");
+  TORCH_CHECK(orders.is_cuda() && orders.scalar_type() == at::kInt && orders.dim() == 2 && orders.size(1) == t_count,
+              "converge: orders must be (R, T) int32 on the GPU");
+  const int64_t n_rep = orders.size(0);
+  TORCH_CHECK(n_rep >= 1 && n_rep <= 4096, "converge: R must be in 1..4096");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == at::kInt && counts.dim() == 1,
+              "converge: counts must be (K,) int32 on the GPU");
+  const int64_t n_cnt = counts.size(0);
+  TORCH_CHECK(n_cnt >= 1 && n_cnt <= 32, "converge: K must be in 1..32");
+  TORCH_CHECK(rep_groups >= 1 && rep_groups <= 1024, "converge: rep_groups must be in 1..1024");
+  auto pp = probs.contiguous(), oo = orders.contiguous(), cc = counts.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.dim() == 1 && yy.size(0) == n, "converge: y must be (n,) on the GPU");
+  const at::DeviceGuard guard(pp.device());
+  auto out = at::zeros({n_rep, n_cnt, 11}, pp.options().dtype(at::kLong));
+  check(apneauq::launch_converge(pp.data_ptr<float>(), yy.data_ptr<int>(), oo.data_ptr<int>(), cc.data_ptr<int>(),
+                                 (int)t_count, (int)n, (int)n_rep, (int)n_cnt, (int)rep_groups,
+                                 reinterpret_cast<long long*>(out.data_ptr<int64_t>()), cur_stream()),
+        "converge");
   return out;
 }
 
@@ -1301,6 +1335,7 @@ TORCH_LIBRARY(apneauq, m) {
   m.def("calib_bootstrap(Tensor rec, Tensor? idx, int seed, int n_boot, int n_global, int lo, int n_bins, int n_thr, int slices) -> Tensor");
   m.def("patient_reduce(Tensor probs, Tensor m, Tensor y, Tensor code, int n_pat) -> (Tensor, Tensor)");
   m.def("patient_bootstrap(Tensor prec, Tensor? idx, int seed, int n_boot) -> Tensor");
+  m.def("converge(Tensor probs, Tensor y, Tensor orders, Tensor counts, int rep_groups) -> Tensor");
   m.def("fused_layout() -> int[]", &fused_layout);
   m.def("fused_layout_x3() -> int[]", &fused_layout_x3);
   m.def("fused_tiled_x3_forward(Tensor x, Tensor blob, int net, int n_pass, int window_offset, int pass_offset, "
@@ -1366,6 +1401,7 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("calib_bootstrap", &calib_bootstrap);
   m.impl("patient_reduce", &patient_reduce);
   m.impl("patient_bootstrap", &patient_bootstrap);
+  m.impl("converge", &converge);
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_multi", &adam_step_multi);
   m.impl("bump_counters", &bump_counters);

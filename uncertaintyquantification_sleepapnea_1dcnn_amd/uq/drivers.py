@@ -168,3 +168,40 @@ def convergence_sweep(predict_fn, counts, X_unbalanced, y_unbalanced, X_balanced
         os.makedirs(d, exist_ok=True)
     df.to_csv(output_csv, index=False)
     return df
+
+
+def convergence_from_predictions(pred_unbalanced, y_unbalanced, pred_balanced=None, y_balanced=None, counts=None,
+                                 output_csv: str = "./convergence.csv", n_orders: int = 100, seed: int = 2025):
+    """The convergence CSV from predictions that exist already: ``(T, N[, 1])`` arrays as the drivers dump them.
+
+    ``N, Variance_Unbalanced, Variance_Balanced`` are the overall mean variances of the first N passes in
+    the order as run, which is what :func:`convergence_sweep` gives when every count reuses the first N
+    passes; ``Variance_*_mean``, ``_lower`` and ``_upper`` are the mean and the 2.5 / 97.5 percentiles over
+    ``n_orders`` random N-subsets (``uq/convergence.py``).  Without a balanced set its columns are NaN.
+    ``analysis.figures.plot_variance_convergence`` reads the file as it reads the sweep's."""
+    from . import convergence as CV
+
+    pu = CV.on_device(pred_unbalanced)
+    cs = CV.default_counts(pu.shape[0], counts)
+    cols = {"N": [int(k) for k in cs]}
+    for name, pred, y in (("Unbalanced", pu, y_unbalanced), ("Balanced", pred_balanced, y_balanced)):
+        if pred is None:
+            v = np.full((2, len(cs)), np.nan)
+        else:
+            pred = CV.on_device(pred)
+            if pred.shape[0] != pu.shape[0]:
+                raise ValueError(f"the balanced set has {pred.shape[0]} passes, the unbalanced {pu.shape[0]}")
+            v = CV.convergence_curves(pred, y, cs, n_orders, seed)["overall_mean_variance"]
+        rnd = v[1:] if v.shape[0] > 1 else v
+        cols[f"Variance_{name}"] = v[0]
+        cols[f"Variance_{name}_mean"] = np.clip(rnd.mean(0), rnd.min(0), rnd.max(0))   # rounding of equal values
+        cols[f"Variance_{name}_lower"] = np.percentile(rnd, 2.5, axis=0)
+        cols[f"Variance_{name}_upper"] = np.percentile(rnd, 97.5, axis=0)
+    order = ["N", "Variance_Unbalanced", "Variance_Balanced"]
+    df = pd.DataFrame(cols)
+    df = df[order + [c for c in df.columns if c not in order]]
+    d = os.path.dirname(output_csv)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    df.to_csv(output_csv, index=False)
+    return df
