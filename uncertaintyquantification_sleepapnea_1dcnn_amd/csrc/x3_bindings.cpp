@@ -9,12 +9,14 @@
 #include <hip/hip_runtime_api.h>
 
 #include "x3_args.h"
+#include "x3_dense_map.h"
 
 namespace apneauq {
 int x3_lds_bytes(int layer);
 int x3_tile_samples(int layer);
 int x3_wg_per_cu(int layer);
-hipError_t x3_launch_layer(int layer, const x3::LayerArgs& A, int grid, hipStream_t stream);
+bool x3_has_dense(int layer);
+hipError_t x3_launch_layer(int layer, const x3::LayerArgs& A, int grid, bool dense_rows, hipStream_t stream);
 hipError_t x3_launch_l1(const x3::L1Args& A, hipStream_t stream);
 hipError_t x3_launch_aff(const x3::AffArgs& A, hipStream_t stream);
 hipError_t x3_launch_head(const x3::HeadArgs& A, hipStream_t stream);
@@ -48,13 +50,18 @@ void x3_layer(int64_t layer, const at::Tensor& in, at::Tensor& out, const at::Te
               bool in_shared, int64_t thr_in, int64_t thr_out, int64_t seed, int64_t pass_base,
               int64_t window_offset, int64_t grid, const c10::optional<at::Tensor>& smax_in,
               const c10::optional<at::Tensor>& amax_in, const c10::optional<at::Tensor>& smax_out,
-              const c10::optional<at::Tensor>& gscale_in, bool sign_in, bool sign_out) {
+              const c10::optional<at::Tensor>& gscale_in, bool sign_in, bool sign_out, bool dense_rows) {
   TORCH_CHECK(layer >= 1 && layer <= 5, "x3_layer: layer must be 1..5 (block 2..6)");
   TORCH_CHECK(n_win >= 1 && groups >= 1, "x3_layer: empty launch");
   const int cin = kCh[layer], cout = kCh[layer + 1], ks = kKs[layer];
   const int64_t samples = n_win * groups, samples_in = in_shared ? n_win : samples;
   const int ts = apneauq::x3_tile_samples((int)layer);
-  const int64_t tpg = (n_win + ts - 1) / ts;
+  // dense_rows: tiles of 64 ts consecutive rows of the group's dense row space (60 per window) instead
+  // of ts whole 64-row window slots (csrc/x3_dense_map.h); the batch-moment kernels of a layer that has it
+  TORCH_CHECK(!dense_rows || apneauq::x3_has_dense((int)layer), "x3_layer: layer ", layer,
+              " has no dense-row kernel");
+  TORCH_CHECK(!dense_rows || n_win < (int64_t(1) << 24), "x3_layer: too many windows for dense rows");
+  const int64_t tpg = dense_rows ? apneauq::x3::dense::tiles(n_win, 64 * ts) : (n_win + ts - 1) / ts;
   TORCH_CHECK(tpg * groups < (int64_t(1) << 31), "x3_layer: too many tiles");
   const int64_t wgroups = w_gstride ? groups : 1, pgroups = p_gstride ? groups : 1;
   need(in, at::kFloat, samples_in * 60 * cin, "x3_layer: in");
@@ -81,6 +88,8 @@ void x3_layer(int64_t layer, const at::Tensor& in, at::Tensor& out, const at::Te
     need(*amax_in, at::kFloat, (aff_gstride ? groups : 1) * 2, "x3_layer: amax_in");
   }
   // or: a per-group prescale folded into aff_in (batch moments; x3_aff gscale)
+  TORCH_CHECK(!(dense_rows && (pre || (smax_out.has_value() && smax_out->defined()))),
+              "x3_layer: the per-sample prescale kernels keep whole-window slots");
   const bool gpre = gscale_in.has_value() && gscale_in->defined();
   TORCH_CHECK(!(pre && gpre), "x3_layer: per-sample and per-group prescale are exclusive");
   if (gpre) need(*gscale_in, at::kFloat, aff_gstride ? groups : 1, "x3_layer: gscale_in");
@@ -123,7 +132,7 @@ void x3_layer(int64_t layer, const at::Tensor& in, at::Tensor& out, const at::Te
   A.seed = (unsigned long long)seed;
   int g = grid > 0 ? (int)grid : num_cus(in) * apneauq::x3_wg_per_cu((int)layer);
   if (g > A.total_tiles) g = A.total_tiles;
-  check(apneauq::x3_launch_layer((int)layer, A, g, cur_stream()), "x3_layer");
+  check(apneauq::x3_launch_layer((int)layer, A, g, dense_rows, cur_stream()), "x3_layer");
 }
 
 void x3_l1(const at::Tensor& x, const at::Tensor& w, const at::Tensor& b, at::Tensor& out,
@@ -209,6 +218,7 @@ void x3_head(const at::Tensor& sums, const at::Tensor& aff, int64_t aff_gstride,
 }
 
 int64_t x3_lds(int64_t layer) { return apneauq::x3_lds_bytes((int)layer); }
+bool x3_has_dense(int64_t layer) { return apneauq::x3_has_dense((int)layer); }
 
 }  // namespace
 
@@ -216,7 +226,8 @@ TORCH_LIBRARY_FRAGMENT(apneauq, m) {
   m.def("x3_layer(int layer, Tensor input, Tensor(a!) out, Tensor wfrag, int w_gstride, Tensor bias, Tensor wscale, "
         "int p_gstride, Tensor aff_in, int aff_gstride, Tensor(b!)? stats, int n_win, int groups, bool in_shared, "
         "int thr_in, int thr_out, int seed, int pass_base, int window_offset, int grid, Tensor? smax_in=None, "
-        "Tensor? amax_in=None, Tensor(c!)? smax_out=None, Tensor? gscale_in=None, bool sign_in=False, bool sign_out=False) -> ()");
+        "Tensor? amax_in=None, Tensor(c!)? smax_out=None, Tensor? gscale_in=None, bool sign_in=False, bool sign_out=False, "
+        "bool dense_rows=False) -> ()");
   m.def("x3_l1(Tensor x, Tensor w, Tensor b, Tensor(a!) out, Tensor(b!)? stats, int n_win, int groups, "
         "Tensor(c!)? smax=None) -> ()");
   m.def("x3_aff(Tensor? stats, Tensor gamma, Tensor beta, Tensor(a!) mmean, Tensor(b!) mvar, Tensor(c!) aff, int C, "
@@ -225,6 +236,7 @@ TORCH_LIBRARY_FRAGMENT(apneauq, m) {
   m.def("x3_head(Tensor sums, Tensor aff, int aff_gstride, Tensor dw, Tensor db, int p_gstride, Tensor(a!) out, "
         "int n_win, int groups, bool logits) -> ()");
   m.def("x3_lds(int layer) -> int", &x3_lds);
+  m.def("x3_has_dense(int layer) -> bool", &x3_has_dense);
 }
 
 TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {

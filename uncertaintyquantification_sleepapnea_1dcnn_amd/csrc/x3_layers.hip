@@ -30,6 +30,19 @@
 //   * one persistent workgroup per CU (7-8 MFMA waves + 4 loader waves) walks a contiguous range of
 //     tiles; a tile = S (2 or 4) samples of one group (MC-Dropout pass or ensemble member) = 64 S GEMM
 //     rows, every sample a 64-row slot (60 time steps + 4 zero rows, the 'same' padding halo);
+//   * dense rows (DENSE, the batch-moment kernels of blocks 2..5, picked per call): the tile is 64 S
+//     consecutive rows of the group's dense row space instead (row d = window d / 60, step d % 60), so
+//     none of its GEMM rows is a halo row: 6.25 % fewer tiles at the same wave tiling, accumulators and
+//     tile size.  A tile starts anywhere inside a window.  In LDS the windows it touches (at most 4 / 6
+//     for 128 / 256 rows) keep fixed 64-row slots relative to the first one, so the zero rows never
+//     move and are never written (a compact layout would have to re-zero them every chunk); the staging
+//     writes the tile's rows plus up to PAD rows past either edge where their window also owns a row of
+//     the tile, and the B-fragment address of a lane's row tile is 4 rows further down per window
+//     boundary crossed (one register per row tile, recomputed per chunk).  Stored outputs are bitwise
+//     those of the slot mapping (the k-order of an output element does not depend on the row tile that
+//     holds it); only the grouping of the fp32 per-tile moment partials differs.  Index map:
+//     x3_dense_map.h; measurements: profiles/x3_dense_rows.md.  Block 6 (per-sample masked sums) and the
+//     per-sample-prescale variants (bitwise chunk invariance, whole-slot prescale) keep slots;
 //   * the input channels stream through LDS in chunks of 32, double-buffered: while the MFMA waves
 //     consume chunk c, the loader waves write chunk c+1 (BN affine + dropout + fp16 split of registers
 //     loaded one chunk earlier) and issue the HBM loads of chunk c+2; one LDS-only barrier per chunk,
@@ -42,6 +55,7 @@
 //     that each weight fragment is re-read by at most WM waves of the 256-row tile.
 #include "common.h"
 #include "x3_args.h"
+#include "x3_dense_map.h"
 
 namespace apneauq {
 namespace x3 {
@@ -82,8 +96,9 @@ __host__ __device__ constexpr int buf_bytes(int S, int ck) { return lds_rows(S) 
 // + per-workgroup fp64 moment sums [2][COUT]
 // two LDS chunk buffers, the workgroup's fp64 moment sums, and the epilogue down-scale factors of the
 // two most recently staged tiles ([2][S] floats, written by the staging waves)
-__host__ __device__ constexpr int lds_bytes(int S, int cout, int ck) {
-  return 2 * buf_bytes(S, ck) + 2 * cout * 8 + 2 * S * 4;
+// (dense-row tiles: the slots of every window a tile can touch, x3_dense_map.h)
+__host__ __device__ constexpr int lds_bytes(int S, int cout, int ck, bool dense_rows = false) {
+  return 2 * (dense_rows ? dense::lds_rows(kSR * S) * row_bytes(ck) : buf_bytes(S, ck)) + 2 * cout * 8 + 2 * S * 4;
 }
 
 // global-address-space load (keeps global_load_*, never flat_*)
@@ -131,20 +146,30 @@ constexpr int waves_per_eu() { return NW * WPC > 8 ? (NW * WPC + 3) / 4 : NW * W
 constexpr int loaders(int lw) { return lw > 0 ? lw : 0; }
 // PS: the per-sample prescale (moving statistics) is compiled in; without it (batch moments: per-group
 // prescale folded into the affine) the kernel has the registers of its tracking for other uses.
-template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS>
+// DENSE: the tile is 64 S consecutive rows of the group's dense row space (window d / 60, step d % 60)
+// instead of S whole 64-row sample slots: no GEMM row is a halo row (x3_dense_map.h).
+template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS, bool DENSE = false>
 __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN + loaders(LW), WPC>())) void layer_kernel(
     const LayerArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NWM = WM * WN, NW = NWM + loaders(LW), kThreads = NW * 64;
   constexpr int kCK = CK, kRowB = row_bytes(CK), NQ = CK / 32, kQ = CK / 4;  // 32-ch sub-chunks, quads / row
-  constexpr int kS = S, kBufB = buf_bytes(S, CK), kValidRows = S * kL, kUnits = kValidRows * kQ;
+  constexpr int PAD = (KS - 1) / 2, kRows = kSR * S;  // GEMM rows per tile
+  static_assert(!DENSE || (!PS && !LAST), "dense rows: batch-moment blocks 2..5 only");
+  constexpr int kS = S, kBufB = DENSE ? dense::lds_rows(kRows) * kRowB : buf_bytes(S, CK);
+  // staged rows per chunk: the samples' time steps (dense rows: every row of the tile, see kMainU)
+  constexpr int kValidRows = DENSE ? kRows : S * kL, kUnits = kValidRows * kQ;
   // staging waves: the LW loader waves, else MFMA waves 0..SW-1 (one per SIMD by default)
   constexpr int SW = LW > 0 ? LW : LW < 0 ? (-LW < NW ? -LW : NW) : (kStagers < NW ? kStagers : NW);
   constexpr int kSBase = LW > 0 ? NWM * 64 : 0;              // first staging thread
   constexpr int kST = SW * 64;                                // staging threads
-  constexpr int kNU = (kUnits + kST - 1) / kST;              // 16-B staging units per staging thread
+  // 16-B staging units per staging thread.  Dense rows: kMainU units tile the rows of the tile exactly,
+  // and one more holds the PAD edge rows either side of it, on the first staging wave(s) only
+  constexpr int kMainU = (kUnits + kST - 1) / kST, kNU = kMainU + (DENSE ? 1 : 0);
+  constexpr int kEdgeWaves = (2 * PAD * kQ + 63) / 64;
+  static_assert(!DENSE || (kUnits % kST == 0 && kEdgeWaves <= SW), "dense rows: whole staging steps per tile");
   static_assert(kST % kQ == 0 && (CK == 32 || CK == 64), "a staging thread keeps one channel quad");
-  constexpr int NCH = CIN / kCK, NCTA = COUT / 16, NCT = NCTA / WN, NRT = 4 * S / WM, PAD = (KS - 1) / 2;
+  constexpr int NCH = CIN / kCK, NCTA = COUT / 16, NCT = NCTA / WN, NRT = 4 * S / WM;
   constexpr int NSTEP = NCH * NQ * KS;  // k-steps (32 input channels x one tap) per tile
   // MFMA issue order: row tiles in groups of RG so that >= 4 accumulators rotate (dependent-issue
   // latency); B fragments double-buffered one group ahead when the accumulators leave room
@@ -174,7 +199,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   __syncthreads();
 
   const int wg = xcd_wg();
-  const int tpg = (A.n_win + S - 1) / S;  // tiles per group at this kernel's tile size
+  // tiles per group at this kernel's tile size
+  const int tpg = DENSE ? (int)dense::tiles(A.n_win, kRows) : (A.n_win + S - 1) / S;
   const int total_tiles = tpg * A.groups;
   const int t_begin = (int)((long long)wg * total_tiles / gridDim.x);
   const int t_end = (int)((long long)(wg + 1) * total_tiles / gridDim.x);
@@ -185,6 +211,18 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   // channel quad q = i % 8) of every chunk
   const bool loader = LW > 0 && wave >= NWM;
   const bool stager = LW > 0 ? loader : wave < SW;
+  const bool edge_wave = DENSE && wave >= kSBase / 64 && wave - kSBase / 64 < kEdgeWaves;  // wave-uniform
+  // dense rows: local dense index dl of unit u of staging thread tid (off: the tile's start inside its first
+  // window); false where the thread has no such unit
+  auto dense_unit = [&](int u, int tid, int off, int& dl) -> bool {
+    const int r = tid / kQ;
+    if (u < kMainU) {
+      dl = off + r + (kST / kQ) * u;
+      return true;
+    }
+    dl = r < PAD ? off - PAD + r : off + kRows - PAD + r;
+    return edge_wave && r < 2 * PAD && dense::staged(dl, off, kRows, PAD);
+  };
   // staging register set: the chunk's 16-B units + the BN affine (scale, shift) x 1/(1-p) of the
   // thread's 4 channels
   struct Stage {
@@ -210,7 +248,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   auto load_chunk = [&](int tile, int c, Stage& R) {
     const int tid = opaque_tid() - kSBase, q = tid % kQ;
     const int g = tile / tpg;
-    const int w0 = (tile - g * tpg) * kS;
+    const int w0 = (tile - g * tpg) * (DENSE ? kRows : kS);  // first window / first dense row of the tile
     const float* af = A.aff_in + (long long)g * A.aff_gstride + c * kCK + 4 * q;
     R.a = gld<f32x4>(af);
     R.b = gld<f32x4>(af + CIN);
@@ -218,7 +256,15 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     for (int u = 0; u < kNU; ++u) {
       const int ri = tid / kQ + (kST / kQ) * u;
       R.v[u] = f32x4{-0.f, -0.f, -0.f, -0.f};
-      if (ri < kValidRows) {
+      if constexpr (DENSE) {
+        // w0 = the tile's first dense row; dl counts from the first row of the first window it touches
+        const int wf = w0 / kL, off = w0 - wf * kL;
+        int dl;
+        if (dense_unit(u, tid, off, dl) && wf + dense::slot_of(dl) < A.n_win) {
+          const long long r0 = (A.in_shared ? 0ll : (long long)g * A.n_win * kL) + wf * kL;
+          R.v[u] = gld<f32x4>(A.in + (r0 + dl) * CIN + c * kCK + 4 * q);
+        }
+      } else if (ri < kValidRows) {
         const int s = ri / kL, t = ri - s * kL, w = w0 + s;
         if (w < A.n_win) {
           const long long si = A.in_shared ? w : (long long)g * A.n_win + w;
@@ -230,7 +276,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   auto store_chunk = [&](int tile, int c, char* buf, const Stage& R) {
     const int tid = opaque_tid() - kSBase, q = tid % kQ;
     const int g = tile / tpg;
-    const int w0 = (tile - g * tpg) * kS;
+    const int w0 = (tile - g * tpg) * (DENSE ? kRows : kS);
     if (tile != key_tile) {  // workgroup-uniform
       const unsigned skey = stream_key(A.seed, A.layer - 1, A.pass_base + g);
       skey_tile = skey;
@@ -239,8 +285,10 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       if (A.gscale_in != nullptr) ws0 *= A.gscale_in[A.aff_gstride ? g : 0];
 #pragma unroll
       for (int i = 0; i < kSP; ++i) sa_pack[i] = 0u;
+      // dense rows: one epilogue factor per tile (the prescale is per group)
+      if (DENSE && tid == 0) wsc[(tile & 1) * kS] = ws0;
 #pragma unroll
-      for (int s = 0; s < kS; ++s) {
+      for (int s = 0; s < (DENSE ? 0 : kS); ++s) {
         skeys[s] = sample_key(skey, A.window_offset + w0 + s);
         int sa = 0;
         if (prescale && w0 + s < A.n_win) {
@@ -257,8 +305,16 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
 #pragma unroll
     for (int u = 0; u < kNU; ++u) {
       const int ri = tid / kQ + (kST / kQ) * u;
-      if (ri >= kValidRows) continue;
-      const int s = ri / kL, t = ri - s * kL, w = w0 + s;
+      int s, t, w, lrow;  // window slot of the tile, time step, window, LDS row
+      if constexpr (DENSE) {
+        const int wf = w0 / kL, off = w0 - wf * kL;
+        int dl;
+        if (!dense_unit(u, tid, off, dl)) continue;
+        s = dense::slot_of(dl), t = dl - s * kL, w = wf + s, lrow = dense::lds_row(dl);
+      } else {
+        if (ri >= kValidRows) continue;
+        s = ri / kL, t = ri - s * kL, w = w0 + s, lrow = kHalo + s * kSR + t;
+      }
       const f32x4 v = R.v[u];
       bool keep[4];
       if (hash_in) {
@@ -313,7 +369,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
         (p ? hi.y : hi.x) = u;
         (p ? lo.y : lo.x) = l;
       }
-      char* row = buf + (kHalo + s * kSR + t) * kRowB + 8 * q;
+      char* row = buf + lrow * kRowB + 8 * q;
       *reinterpret_cast<uint2*>(row) = hi;
       *reinterpret_cast<uint2*>(row + 2 * kCK) = lo;
     }
@@ -345,7 +401,15 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   // wnxt: the next tile's (prefetch across the tile boundary).  hook() runs after tap KS/2: the staging
   // waves write the NEXT chunk into the other LDS buffer there, so that VALU / LDS-write work overlaps
   // the partner wave's MFMAs instead of sitting between two barriers.
-  auto compute_chunk = [&](int c, const char* buf, const gf16x8* wcur, const gf16x8* wnxt, auto&& hook) {
+  // dense rows: row tile rt of the lane lies 4 (dl / 60) LDS rows further down, dl = off + its tile row
+  // (off: the tile's start inside its first window); changes per tile only
+  auto compute_chunk = [&](int c, int off, const char* buf, const gf16x8* wcur, const gf16x8* wnxt, auto&& hook) {
+    const char* bp[DENSE ? NRT : 1];  // the lane's base address per row tile
+    if constexpr (DENSE) {
+#pragma unroll
+      for (int rt = 0; rt < NRT; ++rt)
+        bp[rt] = buf + bofs + (off + (dense::kSlot - kL) * ((off + (rt0 + rt) * 16 + m) / kL)) * kRowB;
+    }
 #pragma unroll
     for (int kk = 0; kk < NQ * KS; ++kk) {
       const int q2 = kk / KS, j = kk - q2 * KS;  // 32-channel sub-chunk, tap
@@ -361,8 +425,9 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       // row tiles in groups of RG: the 3 x NCT x RG MFMAs of a group cycle through NCT x RG
       // accumulators, so a dependent MFMA follows its predecessor >= 4 issues later
       auto ldb = [&](int rt, f16x8& h_, f16x8& l_) {
-        h_ = *reinterpret_cast<const f16x8*>(bb + (rt * 16 + j) * kRowB);
-        l_ = *reinterpret_cast<const f16x8*>(bb + (rt * 16 + j) * kRowB + 2 * kCK);
+        const char* br = DENSE ? bp[rt] + q2 * 64 : bb;
+        h_ = *reinterpret_cast<const f16x8*>(br + (rt * 16 + j) * kRowB);
+        l_ = *reinterpret_cast<const f16x8*>(br + (rt * 16 + j) * kRowB + 2 * kCK);
       };
       f16x8 bh[RG], bl[RG];
 #pragma unroll
@@ -410,12 +475,12 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   auto epilogue = [&](int tile) {
     const int lane = opaque_tid() & 63, m = lane & 15, h = lane >> 4;
     const int g = tile / tpg;
-    const int w0 = (tile - g * tpg) * kS;
+    const int w0 = (tile - g * tpg) * (DENSE ? kRows : kS);  // first window / first dense row of the tile
     // undo the weight prescale 2^sw and each sample's activation prescale 2^sa (exact powers of two;
     // the factors were put in LDS by the staging waves)
     float wsq[NRT / 4];
 #pragma unroll
-    for (int q = 0; q < NRT / 4; ++q) wsq[q] = wsc[(tile & 1) * kS + (rt0 >> 2) + q];
+    for (int q = 0; q < NRT / 4; ++q) wsq[q] = wsc[(tile & 1) * kS + (DENSE ? 0 : (rt0 >> 2) + q)];
     const bool track = PS && !LAST && A.smax_out != nullptr;
     float mxs[NRT / 4];  // max of R_l per sample slot of the wave (range-safe split of the next block)
 #pragma unroll
@@ -426,12 +491,17 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     const bool drop = (LAST || A.sign_out) && A.thr_out != 0u;
     // a wave's row tiles cover whole 64-row sample slots (NRT % 4 == 0): the sample of row tile rt is
     // wave-uniform, so its dropout key is computed once per sample (scalar ALU), not per (ct, rt, lane)
-    unsigned skeys[NRT / 4];
+    // dense rows: the window of a row is per lane and row tile; the keys of the (few) windows the tile
+    // touches are still wave-uniform, and a lane selects among them
+    constexpr int NKEY = DENSE ? dense::max_windows(kRows) : NRT / 4;
+    const int wf = DENSE ? w0 / kL : 0, off = DENSE ? w0 - wf * kL : 0;
+    unsigned skeys[NKEY];
     if (drop) {
       const unsigned skey = stream_key(A.seed, A.layer, A.pass_base + g);
 #pragma unroll
-      for (int q = 0; q < NRT / 4; ++q)
-        skeys[q] = sample_key(skey, A.window_offset + w0 + (rt0 >> 2) + q);
+      for (int q = 0; q < NKEY; ++q)
+        skeys[q] = DENSE ? __builtin_amdgcn_readfirstlane(sample_key(skey, A.window_offset + wf + q))
+                         : sample_key(skey, A.window_offset + w0 + (rt0 >> 2) + q);
     }
     // channel-tile outer: only one tile's 4 channels of sums are live at a time
 #pragma unroll
@@ -439,17 +509,32 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       const int co0 = (ct0 + ct) * 16 + 4 * h;
       const f32x4 b4 = gld<f32x4>(bias + co0);
       f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1, k1 = s1, k0 = s1;
+      // dense rows: (window, step, key) of the lane's row tiles are recomputed per channel tile (a few
+      // full-rate VALU ops each) instead of being kept in NRT registers beside the accumulators
+      int mo = m;
+      if constexpr (DENSE) asm volatile("" : "+v"(mo));
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt) {
-        const int s = (rt0 + rt) >> 2, t = (((rt0 + rt) & 3) << 4) + m, w = w0 + s;
-        const bool valid = t < kL && w < A.n_win;
+        int t, w, sl = 0;
+        bool valid;
+        if constexpr (DENSE) {
+          const int dl = off + (rt0 + rt) * 16 + mo;
+          sl = dense::slot_of(dl), w = wf + sl, t = dl - sl * kL, valid = w < A.n_win;
+        } else {
+          const int s = (rt0 + rt) >> 2;
+          t = (((rt0 + rt) & 3) << 4) + m, w = w0 + s, valid = t < kL && w < A.n_win;
+        }
         f32x4 r;
 #pragma unroll
         for (int e = 0; e < 4; ++e) r[e] = fmaxf(__builtin_fmaf(acc[ct][rt][e], wsq[rt >> 2], b4[e]), 0.f);
         acc[ct][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
         bool keep[4] = {true, true, true, true};
         if (drop) {
-          const unsigned key = skeys[rt >> 2];
+          unsigned key = skeys[DENSE ? 0 : rt >> 2];
+          if constexpr (DENSE) {
+#pragma unroll
+            for (int q = 1; q < NKEY; ++q) key = sl == q ? skeys[q] : key;
+          }
           const unsigned b01 = dropout_bits2(key, t, co0), b23 = dropout_bits2(key, t, co0 + 2);
           keep[0] = (b01 & 0xFFFFu) >= A.thr_out;
           keep[1] = (b01 >> 16) >= A.thr_out;
@@ -535,6 +620,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   // buf[(it+1) & 1] was last read by compute(it-1), which every wave finished before barrier(it-1).
   const int total = (t_end - t_begin) * NCH;
   auto chunk_tile = [&](int it) { return t_begin + it / NCH; };
+  // dense rows: the tile's start inside its first window
+  auto tile_off = [&](int tile) { return DENSE ? (int)((long long)(tile % tpg) * kRows % kL) : 0; };
   int g_cur = t_begin / tpg;
   if constexpr (LW > 0) {
     // Loader and MFMA waves run the same barrier sequence: one LDS barrier before the first chunk and
@@ -580,7 +667,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       }
       const gf16x8* wcur = wbase(tile);
       const gf16x8* wnxt = wbase(tile + 1 < t_end ? tile + 1 : tile);
-      compute_chunk(c, smem + (it & 1) * kBufB, wcur, wnxt, []() {});
+      compute_chunk(c, tile_off(tile), smem + (it & 1) * kBufB, wcur, wnxt, []() {});
       if (c == NCH - 1) epilogue(tile);
       lds_barrier();
     }
@@ -608,7 +695,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     const gf16x8* wnxt = wbase(tile + 1 < t_end ? tile + 1 : tile);
     char* buf = smem + (it & 1) * kBufB;
     char* nbuf = smem + ((it + 1) & 1) * kBufB;
-    compute_chunk(c, buf, wcur, wnxt, [&]() {
+    compute_chunk(c, tile_off(tile), buf, wcur, wnxt, [&]() {
       if (stager && it + 1 < total) store_chunk(chunk_tile(it + 1), (it + 1) % NCH, nbuf, s0);
     });
     if (c == NCH - 1) epilogue(tile);
@@ -799,11 +886,11 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs A) {
 }
 
 // ------------------------------------------------------------------------------- launch helpers
-template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS>
+template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS, bool DENSE = false>
 hipError_t launch_layer(const LayerArgs& A, int grid, hipStream_t stream) {
-  constexpr int lds = lds_bytes(S, COUT, CK);
+  constexpr int lds = lds_bytes(S, COUT, CK, DENSE);
   static_assert(WPC * lds <= 160 * 1024, "LDS of the workgroups sharing a CU");
-  auto k = layer_kernel<CIN, COUT, KS, S, WM, WN, LAST, LW, CK, WPC, PS>;
+  auto k = layer_kernel<CIN, COUT, KS, S, WM, WN, LAST, LW, CK, WPC, PS, DENSE>;
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -814,12 +901,26 @@ hipError_t launch_layer(const LayerArgs& A, int grid, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// the dense-row instantiation of a layer, compiled only where the layer table asks for it.  A layer
+// without loader waves (block 2) stages on all its MFMA waves there: the extra edge unit beside four
+// stagers' eight units and the NRT B-fragment bases spilled (52 B / lane), with eight stagers' five units
+// the kernel fits (253 VGPRs, no scratch).
+template <bool HAVE, int CIN, int COUT, int KS, int S, int WM, int WN, int LW, int CK, int WPC>
+hipError_t launch_dense(const LayerArgs& A, int grid, hipStream_t stream) {
+  if constexpr (HAVE) {
+    return launch_layer<CIN, COUT, KS, S, WM, WN, false, (LW > 0 ? LW : -(WM * WN)), CK, WPC, false, true>(A, grid, stream);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+
 }  // namespace x3
 
 // Layer table of the reference architecture (cnn_baseline_train.py:59-86), blocks 2..6:
 //   <Cin, Cout, k, samples per tile, wave rows WM, wave channel groups WN, block 6, loader waves LW
 //    (<= 0: no loaders, -LW MFMA waves stage) with / LWB without the per-sample prescale,
-//    input channels per staged chunk CK, persistent workgroups per CU WPC>
+//    input channels per staged chunk CK, persistent workgroups per CU WPC, DENSE: the dense-row
+//    instantiation (batch moments, blocks 2..5) is compiled in and can be picked per call>
 // Each MFMA wave owns (4 S / WM) 16-row tiles x (Cout / 16 / WN) 16-channel tiles; the 64-accumulator-tile
 // layers (Cout 224 / 256) run 2-sample tiles so that the next k-step's weight fragments and the B
 // double-buffer fit beside the accumulators without spilling.  Loader waves (ablation table in
@@ -835,16 +936,16 @@ hipError_t launch_layer(const LayerArgs& A, int grid, hipStream_t stream) {
 #ifdef APNEAUQ_X3_TABLE
 #include APNEAUQ_X3_TABLE
 #else
-#define APNEAUQ_X3_LAYERS(X)                     \
-  X(1, 128, 192, 5, 4, 2, 4, false, -8, 0, 32, 1) \
-  X(2, 192, 224, 3, 2, 1, 7, false, 4, 4, 64, 1) \
-  X(3, 224, 96, 7, 4, 2, 2, false, 4, 4, 32, 1)  \
-  X(4, 96, 256, 9, 2, 1, 8, false, 4, 4, 32, 1)  \
-  X(5, 256, 96, 9, 4, 2, 2, true, 4, 4, 64, 1)
+#define APNEAUQ_X3_LAYERS(X)                           \
+  X(1, 128, 192, 5, 4, 2, 4, false, -8, 0, 32, 1, true) \
+  X(2, 192, 224, 3, 2, 1, 7, false, 4, 4, 64, 1, true)  \
+  X(3, 224, 96, 7, 4, 2, 2, false, 4, 4, 32, 1, true)   \
+  X(4, 96, 256, 9, 2, 1, 8, false, 4, 4, 32, 1, true)   \
+  X(5, 256, 96, 9, 4, 2, 2, true, 4, 4, 64, 1, false)
 #endif
 
 int x3_lds_bytes(int layer) {
-#define APNEAUQ_X3_LDS(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC) \
+#define APNEAUQ_X3_LDS(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
   if (layer == L) return x3::lds_bytes(S, CO, CK);
   APNEAUQ_X3_LAYERS(APNEAUQ_X3_LDS)
 #undef APNEAUQ_X3_LDS
@@ -852,27 +953,39 @@ int x3_lds_bytes(int layer) {
 }
 
 int x3_tile_samples(int layer) {
-#define APNEAUQ_X3_TS(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC) \
+#define APNEAUQ_X3_TS(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
   if (layer == L) return S;
   APNEAUQ_X3_LAYERS(APNEAUQ_X3_TS)
 #undef APNEAUQ_X3_TS
   return 0;
 }
 
+// the layer has a dense-row instantiation (x3_launch_layer dense_rows)
+bool x3_has_dense(int layer) {
+#define APNEAUQ_X3_HD(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
+  if (layer == L) return DENSE && !LAST;
+  APNEAUQ_X3_LAYERS(APNEAUQ_X3_HD)
+#undef APNEAUQ_X3_HD
+  return false;
+}
+
 int x3_wg_per_cu(int layer) {
-#define APNEAUQ_X3_WPC(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC) \
+#define APNEAUQ_X3_WPC(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
   if (layer == L) return WPC;
   APNEAUQ_X3_LAYERS(APNEAUQ_X3_WPC)
 #undef APNEAUQ_X3_WPC
   return 1;
 }
 
-hipError_t x3_launch_layer(int layer, const x3::LayerArgs& A, int grid, hipStream_t stream) {
+hipError_t x3_launch_layer(int layer, const x3::LayerArgs& A, int grid, bool dense_rows, hipStream_t stream) {
   using namespace x3;
   // the per-sample prescale variant only where it is used (moving statistics)
   const bool ps = A.smax_in != nullptr || A.smax_out != nullptr;
-#define APNEAUQ_X3_LAUNCH(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC)                                  \
+#define APNEAUQ_X3_LAUNCH(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE)                                  \
   if (layer == L) {                                                                                       \
+    if (dense_rows)                                                                                       \
+      return ps ? hipErrorInvalidValue                                                                    \
+                : launch_dense<DENSE && !LAST, CI, CO, K, S, WM, WN, LWB, CK, WPC>(A, grid, stream);       \
     return ps ? launch_layer<CI, CO, K, S, WM, WN, LAST, LW, CK, WPC, true>(A, grid, stream)               \
               : launch_layer<CI, CO, K, S, WM, WN, LAST, LWB, CK, WPC, false>(A, grid, stream);            \
   }

@@ -182,6 +182,33 @@ def _sign(l: int, sl: frozenset):
     return (l - 1) in sl and l >= 2, l in sl and l <= 4
 
 
+# layers (x3_layer index 1..4 = blocks 2..5) whose batch-moment kernels (mcd_batch, Deep-Ensemble predict)
+# tile the group's dense row space (window d // 60, step d % 60: no GEMM row is a halo row) instead of
+# whole 64-row window slots (csrc/x3_dense_map.h).  Stored outputs are bitwise those of the slot mapping;
+# only the grouping of the fp32 per-tile moment partials differs.  The default is the set of layers
+# where it measured faster (profiles/x3_dense_rows.md); a layer needs its dense kernel compiled in
+# (csrc/x3_layers.hip layer table).  APNEAUQ_X3_DENSE="1,3" overrides (A/B probes), and so does
+# :func:`set_dense_layers` within a process.  The running-statistics MC Dropout always keeps slots.
+_DENSE_DEFAULT = "1,2,3,4"
+_dense_override: Optional[frozenset] = None
+
+
+def set_dense_layers(layers: Optional[Sequence[int]]) -> Optional[frozenset]:
+    """Pick the dense-row mapping for these x3_layer indices (None: back to the default / environment);
+    returns the previous override."""
+    global _dense_override
+    prev = _dense_override
+    _dense_override = None if layers is None else frozenset(int(l) for l in layers)
+    return prev
+
+
+def _dense_layers() -> frozenset:
+    if _dense_override is not None:
+        return _dense_override
+    v = os.environ.get("APNEAUQ_X3_DENSE", _DENSE_DEFAULT)
+    return frozenset(int(t) for t in v.replace(" ", "").split(",") if t)
+
+
 def _dsc(rate: float) -> float:
     return 1.0 / (1.0 - rate) if rate < 1.0 else 0.0
 
@@ -253,6 +280,7 @@ def mcd_batch(model: X3Model, x: torch.Tensor, n_pass: int, seed: int, pass_base
     eps, mom = float(spec.bn_epsilon), float(spec.bn_momentum)
     seed = int(seed) & ((1 << 63) - 1)
     sl = _sign_layers()
+    dl = _dense_layers()
     out = torch.empty(n_pass, n, dtype=torch.float32, device=model.device)
     # block 1 once: no dropout precedes it, so every pass sees the same R_1 and the same moments
     ws.stats[0].zero_()
@@ -273,7 +301,7 @@ def mcd_batch(model: X3Model, x: torch.Tensor, n_pass: int, seed: int, pass_base
             dst = ws.sums if l == 5 else ws.buf[(l - 1) % 2]
             o.x3_layer(l, src, dst, model.wfrag[l], 0, model.bias[l], model.wscale[l], 0, ws.aff[l - 1],
                        0 if l == 1 else 2 * CH[l], st, n, tc, l == 1, thr[l - 1], thr[l], seed, pb,
-                       int(window_offset), int(grid), None, None, None, ws.gscale[l - 1], *_sign(l, sl))
+                       int(window_offset), int(grid), None, None, None, ws.gscale[l - 1], *_sign(l, sl), l in dl)
             if sync is not None:
                 _sync_stats(sync, st, tc, c)
             g, b, mm, mv = model.bn[l]
@@ -307,6 +335,7 @@ def _mcd_batch_windowed(model: X3Model, x: torch.Tensor, n_pass: int, seed: int,
     eps, mom = float(spec.bn_epsilon), float(spec.bn_momentum)
     seed = int(seed) & ((1 << 63) - 1)
     sl = _sign_layers()
+    dl = _dense_layers()
     out = torch.empty(n_pass, n, dtype=torch.float32, device=model.device)
 
     def run(s: int, e: int, upto: int, pb: int, stats_layer: int) -> None:
@@ -319,7 +348,7 @@ def _mcd_batch_windowed(model: X3Model, x: torch.Tensor, n_pass: int, seed: int,
             o.x3_layer(l, src, dst, model.wfrag[l], 0, model.bias[l], model.wscale[l], 0, ws.aff[l - 1],
                        0 if l == 1 else 2 * CH[l], ws.stats[l] if l == stats_layer else None, m, 1, l == 1,
                        thr[l - 1], thr[l], seed, pb, int(window_offset) + s, 0, None, None, None, ws.gscale[l - 1],
-                       *_sign(l, sl))
+                       *_sign(l, sl), l in dl)
 
     def finish_layer(l: int, repeat: int) -> None:
         if sync is not None:
@@ -438,6 +467,7 @@ def _predict_members(model: X3Model, ws: "_Workspace", x: torch.Tensor, G: int, 
     n = x.shape[0]
     per_member = G > 1
     ps = CH[1:] if per_member else [0] * 6
+    dl = _dense_layers()
     o.zero_buffers([ws.stats[l][: G * STAT_SLOTS * 2 * CH[l + 1]] for l in range(5)])
     g, b, mm, mv = model.bn[5]  # block 6 feeds the fp32 head: no prescale
     o.x3_aff(None, g, b, mm, mv, ws.aff[5], CH[6], G, ps[5], False, 1, 1.0, eps, mom, 1.0, None)
@@ -451,7 +481,7 @@ def _predict_members(model: X3Model, ws: "_Workspace", x: torch.Tensor, G: int, 
         wstride = model.wfrag[l].shape[1] // 8 if per_member else 0
         o.x3_layer(l, src, dst, model.wfrag[l], wstride, model.bias[l], model.wscale[l], ps[l],
                    ws.aff[l - 1], 2 * CH[l] if per_member else 0, ws.stats[l] if l < 5 else None, n, G, False, 0, 0,
-                   0, 0, 0, 0, None, None, None, ws.gscale[l - 1], False, False)
+                   0, 0, 0, 0, None, None, None, ws.gscale[l - 1], False, False, l in dl)
     o.x3_head(ws.sums, ws.aff[5], 2 * CH[6] if per_member else 0, model.dw, model.db, CH[6] if per_member else 0,
               ws.out, n, G, bool(logits))
     return ws.out[: G * n].view(G, 1, n).clone()
