@@ -48,6 +48,37 @@ __host__ __device__ constexpr bool staged(int dl, int off, int rows, int pad) {
   return dl >= 0 && dl >= off - pad && dl < off + rows + pad && dl < kLen * windows(off, rows);
 }
 
+// ---- per-tile row descriptors.  Everything the staging and the epilogue need to know about a row
+// depends on (tile, row) only, not on the chunk or the channel tile, so it is computed once per tile.
+// A row is named by rel = its dense row minus the tile's first (-pad .. rows + pad - 1; dl = off + rel).
+// Its global row is the tile's first global row + rel (linear: no descriptor needed), and it lies inside
+// the group iff rel < rows_left = 60 n_win - first_row(tile) (callers may clamp it to any value above
+// rows + pad), which is the same as window < n_win.
+// Packed word: LDS row (9 bits: lds_rows(256) = 392), time step (6 bits), window slot (3 bits), valid.
+constexpr int kDescStepShift = 9, kDescSlotShift = 15, kDescValidShift = 18;
+__host__ __device__ constexpr unsigned desc_pack(int lrow, int step, int slot, bool valid) {
+  return (unsigned)lrow | (unsigned)step << kDescStepShift | (unsigned)slot << kDescSlotShift |
+         (valid ? 1u : 0u) << kDescValidShift;
+}
+__host__ __device__ constexpr int desc_lds_row(unsigned d) { return (int)(d & 511u); }
+__host__ __device__ constexpr int desc_step(unsigned d) { return (int)(d >> kDescStepShift & 63u); }
+__host__ __device__ constexpr int desc_slot(unsigned d) { return (int)(d >> kDescSlotShift & 7u); }
+__host__ __device__ constexpr bool desc_valid(unsigned d) { return (d >> kDescValidShift & 1u) != 0u; }
+// descriptor of row rel of a tile that starts `off` steps into its first window; valid: the row is staged
+// (staged(), edge rows) and inside the group.  A row that is not staged has descriptor 0.
+__host__ __device__ constexpr unsigned row_desc(int rel, int off, int rows, int pad, int rows_left) {
+  const int dl = off + rel;
+  if (!staged(dl, off, rows, pad)) return 0u;
+  return desc_pack(lds_row(dl), step_of(dl), slot_of(dl), rel < rows_left);
+}
+// whole-window slot tiles (row ri = 60 s + t of the tile's S windows): LDS row kHalo + 64 s + t
+__host__ __device__ constexpr unsigned slot_row_desc(int ri, int rows_left) {
+  return desc_pack(lds_row(ri), step_of(ri), slot_of(ri), ri < rows_left);
+}
+// The mask word of a row: dropout_bits2(key, t, c) = mix32(key ^ (t << 9 | c >> 1)) = mix32(mask_word ^ (c >> 1))
+// for c < 1024, so a row keeps key ^ (t << 9) and a channel pair costs one xor and one mix32.
+__host__ __device__ constexpr unsigned mask_word(unsigned sample_key, int step) { return sample_key ^ ((unsigned)step << 9); }
+
 }  // namespace dense
 }  // namespace x3
 }  // namespace apneauq

@@ -38,7 +38,11 @@
 //     move and are never written (a compact layout would have to re-zero them every chunk); the staging
 //     writes the tile's rows plus up to PAD rows past either edge where their window also owns a row of
 //     the tile, and the B-fragment address of a lane's row tile is 4 rows further down per window
-//     boundary crossed (one register per row tile, recomputed per chunk).  Stored outputs are bitwise
+//     boundary crossed (one register per row tile, recomputed per chunk).  What staging and epilogue need
+//     per row (LDS row, validity, the dropout mask words key ^ (t << 9) of the input and output streams)
+//     depends on (tile, row) only: the staging waves write it once per tile, one thread per row, into
+//     two small LDS tables that every chunk and channel tile looks up, and global rows are addressed
+//     linearly from the tile's first row (profiles/x3_row_descriptors.md).  Stored outputs are bitwise
 //     those of the slot mapping (the k-order of an output element does not depend on the row tile that
 //     holds it); only the grouping of the fp32 per-tile moment partials differs.  Index map:
 //     x3_dense_map.h; measurements: profiles/x3_dense_rows.md.  Block 6 (per-sample masked sums) and the
@@ -96,9 +100,13 @@ __host__ __device__ constexpr int buf_bytes(int S, int ck) { return lds_rows(S) 
 // + per-workgroup fp64 moment sums [2][COUT]
 // two LDS chunk buffers, the workgroup's fp64 moment sums, and the epilogue down-scale factors of the
 // two most recently staged tiles ([2][S] floats, written by the staging waves)
-// (dense-row tiles: the slots of every window a tile can touch, x3_dense_map.h)
-__host__ __device__ constexpr int lds_bytes(int S, int cout, int ck, bool dense_rows = false) {
-  return 2 * (dense_rows ? dense::lds_rows(kSR * S) * row_bytes(ck) : buf_bytes(S, ck)) + 2 * cout * 8 + 2 * S * 4;
+// (dense-row tiles: the slots of every window a tile can touch, x3_dense_map.h), and the row tables of
+// the two most recently staged tiles (written by the staging waves): [2][64 S] output-mask words of the
+// tile's rows, [2][tab_rows] descriptor and input-mask word of every staged row
+__host__ __device__ constexpr int tab_rows(int S, int ks) { return kSR * S + (ks - 1); }  // the tile's rows + 2 PAD
+__host__ __device__ constexpr int lds_bytes(int S, int cout, int ck, int ks, bool dense_rows = false) {
+  return 2 * (dense_rows ? dense::lds_rows(kSR * S) * row_bytes(ck) : buf_bytes(S, ck)) + 2 * cout * 8 + 2 * S * 4 +
+         (dense_rows ? 2 * kSR * S * 4 + 2 * tab_rows(S, ks) * 8 : 0);
 }
 
 // global-address-space load (keeps global_load_*, never flat_*)
@@ -186,6 +194,20 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   double* st = reinterpret_cast<double*>(smem + 2 * kBufB);  // [2][COUT] per-workgroup moment sums
   // [tile & 1][sample of the tile]: wscale x 2^-sa, the epilogue's undo of both prescales
   float* wsc = reinterpret_cast<float*>(smem + 2 * kBufB + 2 * COUT * 8);
+  // Row tables of the dense-row kernels (x3_dense_map.h).  What the staging and the epilogue need to know
+  // about a row depends on (tile, row) only, not on the chunk or the channel tile, so the staging waves
+  // compute it once per tile, one thread per row, and every chunk and channel tile looks it up:
+  //   stab[tile & 1][staged row]  descriptor (LDS row, step, window slot, valid), input-mask word key ^ (t << 9)
+  //   ektab[tile & 1][tile row]   output-mask word where the epilogue draws the block's mask
+  // A tile's tables are written with the last chunk of the tile before it (the first tile's before the
+  // first barrier): one chunk barrier ahead of their first reader, the staging of the tile's chunk 0, and
+  // a whole tile after the last reader of the tables they replace (tile - 2, the parity).  The slot
+  // kernels (block 6, per-sample prescale) keep their per-chunk index math: block 6 measured 0.8 % slower
+  // with the tables (profiles/x3_row_descriptors.md).
+  constexpr int kTabRows = tab_rows(S, KS);
+  static_assert(!DENSE || CIN / CK >= 2, "row tables: a tile's tables are written one chunk of the same workgroup ahead");
+  unsigned* ektab = reinterpret_cast<unsigned*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4);
+  uint2* stab = reinterpret_cast<uint2*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4 + 2 * kRows * 4);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -193,10 +215,6 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   const int ct0 = wn * NCT, rt0 = wm * NRT;
   const int m = lane & 15, h = lane >> 4;
   APNEAUQ_DASSERT(blockDim.x == kThreads);
-
-  for (int i = tid; i < 2 * kBufB / 16; i += kThreads) reinterpret_cast<f32x4*>(smem)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int i = tid; i < 2 * COUT; i += kThreads) st[i] = 0.0;
-  __syncthreads();
 
   const int wg = xcd_wg();
   // tiles per group at this kernel's tile size
@@ -212,16 +230,16 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   const bool loader = LW > 0 && wave >= NWM;
   const bool stager = LW > 0 ? loader : wave < SW;
   const bool edge_wave = DENSE && wave >= kSBase / 64 && wave - kSBase / 64 < kEdgeWaves;  // wave-uniform
-  // dense rows: local dense index dl of unit u of staging thread tid (off: the tile's start inside its first
-  // window); false where the thread has no such unit
-  auto dense_unit = [&](int u, int tid, int off, int& dl) -> bool {
+  // dense rows, unit u of staging thread tid: its row relative to the tile's first row (the edge unit holds
+  // the PAD rows either side of the tile); false where the thread has no such unit
+  auto unit_row = [&](int u, int tid, int& rel) -> bool {
     const int r = tid / kQ;
     if (u < kMainU) {
-      dl = off + r + (kST / kQ) * u;
+      rel = r + (kST / kQ) * u;
       return true;
     }
-    dl = r < PAD ? off - PAD + r : off + kRows - PAD + r;
-    return edge_wave && r < 2 * PAD && dense::staged(dl, off, kRows, PAD);
+    rel = r < PAD ? r - PAD : kRows - PAD + r;
+    return edge_wave && r < 2 * PAD;
   };
   // staging register set: the chunk's 16-B units + the BN affine (scale, shift) x 1/(1-p) of the
   // thread's 4 channels
@@ -245,30 +263,69 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   static_assert(kS <= 8, "packed per-sample exponents");
   constexpr int kSP = (kS + 3) / 4;
   unsigned sa_pack[kSP];
+  // first window / first dense row of a tile, its first window wf, its start inside it, and the rows from
+  // its first row to the end of the group (clamped: only rows of the tile are compared with it)
+  struct Geo {
+    int g, w0, wf, off, rows_left;
+  };
+  auto tile_geo = [&](int tile) {
+    Geo G;
+    G.g = tile / tpg;
+    G.w0 = (tile - G.g * tpg) * (DENSE ? kRows : kS);
+    G.wf = DENSE ? G.w0 / kL : G.w0, G.off = DENSE ? G.w0 - G.wf * kL : 0;
+    const long long left = (long long)(A.n_win - G.wf) * kL - G.off;
+    G.rows_left = (int)(left < 1024 ? left : 1024);
+    return G;
+  };
+  const bool mask_out = DENSE && A.sign_out && A.thr_out != 0u;  // the epilogue draws block l's mask
+  auto write_tables = [&](int tile) {
+    if constexpr (DENSE) {
+      const int tid = opaque_tid() - kSBase;
+      const Geo G = tile_geo(tile);
+      const unsigned ikey = stream_key(A.seed, A.layer - 1, A.pass_base + G.g);
+      const unsigned okey = stream_key(A.seed, A.layer, A.pass_base + G.g);
+#pragma unroll
+      for (int i0 = 0; i0 < kTabRows; i0 += kST) {
+        const int i = i0 + tid, rel = i - PAD;
+        if (i < kTabRows) {
+          const unsigned d = dense::row_desc(rel, G.off, kRows, PAD, G.rows_left);
+          const unsigned win = A.window_offset + G.wf + dense::desc_slot(d);
+          const int t = dense::desc_step(d);
+          stab[(tile & 1) * kTabRows + i] = uint2{d, hash_in ? dense::mask_word(sample_key(ikey, win), t) : 0u};
+          if (mask_out && rel >= 0 && rel < kRows) ektab[(tile & 1) * kRows + rel] = dense::mask_word(sample_key(okey, win), t);
+        }
+      }
+    }
+  };
   auto load_chunk = [&](int tile, int c, Stage& R) {
     const int tid = opaque_tid() - kSBase, q = tid % kQ;
-    const int g = tile / tpg;
-    const int w0 = (tile - g * tpg) * (DENSE ? kRows : kS);  // first window / first dense row of the tile
-    const float* af = A.aff_in + (long long)g * A.aff_gstride + c * kCK + 4 * q;
+    const Geo G = tile_geo(tile);
+    const float* af = A.aff_in + (long long)G.g * A.aff_gstride + c * kCK + 4 * q;
     R.a = gld<f32x4>(af);
     R.b = gld<f32x4>(af + CIN);
+    if constexpr (DENSE) {
+      // the rows of a tile are consecutive rows of the input: row rel of the tile is row row0 + rel
+      const long long row0 = (A.in_shared ? 0ll : (long long)G.g * A.n_win * kL) + G.w0;
+      const float* in = A.in + row0 * CIN + c * kCK + 4 * q;
 #pragma unroll
-    for (int u = 0; u < kNU; ++u) {
-      const int ri = tid / kQ + (kST / kQ) * u;
-      R.v[u] = f32x4{-0.f, -0.f, -0.f, -0.f};
-      if constexpr (DENSE) {
-        // w0 = the tile's first dense row; dl counts from the first row of the first window it touches
-        const int wf = w0 / kL, off = w0 - wf * kL;
-        int dl;
-        if (dense_unit(u, tid, off, dl) && wf + dense::slot_of(dl) < A.n_win) {
-          const long long r0 = (A.in_shared ? 0ll : (long long)g * A.n_win * kL) + wf * kL;
-          R.v[u] = gld<f32x4>(A.in + (r0 + dl) * CIN + c * kCK + 4 * q);
-        }
-      } else if (ri < kValidRows) {
-        const int s = ri / kL, t = ri - s * kL, w = w0 + s;
-        if (w < A.n_win) {
-          const long long si = A.in_shared ? w : (long long)g * A.n_win + w;
-          R.v[u] = gld<f32x4>(A.in + (si * kL + t) * CIN + c * kCK + 4 * q);
+      for (int u = 0; u < kNU; ++u) {
+        int rel;
+        bool have = unit_row(u, tid, rel);
+        if (u >= kMainU) have = have && dense::staged(G.off + rel, G.off, kRows, PAD);
+        R.v[u] = f32x4{-0.f, -0.f, -0.f, -0.f};
+        if (have && rel < G.rows_left) R.v[u] = gld<f32x4>(in + rel * CIN);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < kNU; ++u) {
+        const int ri = tid / kQ + (kST / kQ) * u;
+        R.v[u] = f32x4{-0.f, -0.f, -0.f, -0.f};
+        if (ri < kValidRows) {
+          const int s = ri / kL, t = ri - s * kL, w = G.w0 + s;
+          if (w < A.n_win) {
+            const long long si = A.in_shared ? w : (long long)G.g * A.n_win + w;
+            R.v[u] = gld<f32x4>(A.in + (si * kL + t) * CIN + c * kCK + 4 * q);
+          }
         }
       }
     }
@@ -277,6 +334,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     const int tid = opaque_tid() - kSBase, q = tid % kQ;
     const int g = tile / tpg;
     const int w0 = (tile - g * tpg) * (DENSE ? kRows : kS);
+    // the next tile's tables, one chunk barrier before the staging of its first chunk reads them
+    if (DENSE && c == NCH - 1 && tile + 1 < t_end) write_tables(tile + 1);
     if (tile != key_tile) {  // workgroup-uniform
       const unsigned skey = stream_key(A.seed, A.layer - 1, A.pass_base + g);
       skey_tile = skey;
@@ -302,34 +361,44 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       }
       key_tile = tile;
     }
+    const uint2* tab = stab + (tile & 1) * kTabRows + PAD;
 #pragma unroll
     for (int u = 0; u < kNU; ++u) {
-      const int ri = tid / kQ + (kST / kQ) * u;
-      int s, t, w, lrow;  // window slot of the tile, time step, window, LDS row
+      int s, lrow;      // window slot of the tile, LDS row
+      bool valid;
+      unsigned kt = 0u;  // the row's input-mask word key ^ (t << 9)
       if constexpr (DENSE) {
-        const int wf = w0 / kL, off = w0 - wf * kL;
-        int dl;
-        if (!dense_unit(u, tid, off, dl)) continue;
-        s = dense::slot_of(dl), t = dl - s * kL, w = wf + s, lrow = dense::lds_row(dl);
+        int rel;
+        if (!unit_row(u, tid, rel)) continue;
+        const uint2 e = tab[rel];  // the row's descriptor and mask word
+        if (e.x == 0u) continue;   // a row that is not staged (an LDS row is >= kHalo)
+        s = dense::desc_slot(e.x), lrow = dense::desc_lds_row(e.x), valid = dense::desc_valid(e.x), kt = e.y;
       } else {
+        const int ri = tid / kQ + (kST / kQ) * u;
         if (ri >= kValidRows) continue;
-        s = ri / kL, t = ri - s * kL, w = w0 + s, lrow = kHalo + s * kSR + t;
+        s = ri / kL;
+        const int t = ri - s * kL;
+        lrow = kHalo + s * kSR + t, valid = w0 + s < A.n_win;
+        if (hash_in) {
+          // the sample's key: recomputed per staged unit (batch moments: block 2 -4 % over a select from
+          // the tile's cached keys), or selected from the cache where the prescale needs its registers
+          unsigned k;
+          if constexpr (!PS) {
+            k = sample_key(skey_tile, A.window_offset + w0 + s);
+          } else {
+            k = skeys[0];
+#pragma unroll
+            for (int j = 1; j < kS; ++j) k = s == j ? skeys[j] : k;
+          }
+          kt = dense::mask_word(k, t);
+        }
       }
       const f32x4 v = R.v[u];
       bool keep[4];
       if (hash_in) {
-        // the sample's key: recomputed per staged unit (batch moments: block 2 -4 % over a select from
-        // the tile's cached keys), or selected from the cache where the prescale needs its registers
-        unsigned k;
-        if constexpr (!PS) {
-          k = sample_key(skey_tile, A.window_offset + w);
-        } else {
-          k = skeys[0];
-#pragma unroll
-          for (int j = 1; j < kS; ++j) k = s == j ? skeys[j] : k;
-        }
-        const unsigned b01 = dropout_bits2(k, t, c * kCK + 4 * q);
-        const unsigned b23 = dropout_bits2(k, t, c * kCK + 4 * q + 2);
+        // dropout_bits2(key, t, ch) and (key, t, ch + 2) of the unit's channels ch = c kCK + 4 q
+        const unsigned cp = (unsigned)(c * kCK + 4 * q) >> 1;
+        const unsigned b01 = mix32(kt ^ cp), b23 = mix32(kt ^ (cp + 1u));
         keep[0] = (b01 & 0xFFFFu) >= A.thr_in;
         keep[1] = (b01 >> 16) >= A.thr_in;
         keep[2] = (b23 & 0xFFFFu) >= A.thr_in;
@@ -341,7 +410,6 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
 #pragma unroll
         for (int i = 0; i < 4; ++i) keep[i] = true;
       }
-      const bool valid = w < A.n_win;
       // the sample's exponent: a signed byte of sa_pack (v_bfe_i32), applied exactly by v_ldexp_f32
       int sa = 0;
       if (prescale) {
@@ -491,35 +559,38 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     const bool drop = (LAST || A.sign_out) && A.thr_out != 0u;
     // a wave's row tiles cover whole 64-row sample slots (NRT % 4 == 0): the sample of row tile rt is
     // wave-uniform, so its dropout key is computed once per sample (scalar ALU), not per (ct, rt, lane)
-    // dense rows: the window of a row is per lane and row tile; the keys of the (few) windows the tile
-    // touches are still wave-uniform, and a lane selects among them
-    constexpr int NKEY = DENSE ? dense::max_windows(kRows) : NRT / 4;
-    const int wf = DENSE ? w0 / kL : 0, off = DENSE ? w0 - wf * kL : 0;
+    // dense rows: the window and step of a row are per lane and row tile; the staging waves put the row's
+    // mask word key ^ (t << 9) into the tile's table (ektab), one LDS read per accumulator tile.  The
+    // tile's rows are consecutive rows of the output, and a row is inside the group iff it is one of the
+    // first rows_left of the tile
+    constexpr int NKEY = DENSE ? 1 : NRT / 4;
     unsigned skeys[NKEY];
-    if (drop) {
+    if (!DENSE && drop) {
       const unsigned skey = stream_key(A.seed, A.layer, A.pass_base + g);
 #pragma unroll
-      for (int q = 0; q < NKEY; ++q)
-        skeys[q] = DENSE ? __builtin_amdgcn_readfirstlane(sample_key(skey, A.window_offset + wf + q))
-                         : sample_key(skey, A.window_offset + w0 + (rt0 >> 2) + q);
+      for (int q = 0; q < NKEY; ++q) skeys[q] = sample_key(skey, A.window_offset + w0 + (rt0 >> 2) + q);
     }
+    const long long left = (long long)A.n_win * kL - w0;
+    const int rows_left = DENSE ? (int)(left < kRows ? left : kRows) : 0;
     // channel-tile outer: only one tile's 4 channels of sums are live at a time
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
       const int co0 = (ct0 + ct) * 16 + 4 * h;
       const f32x4 b4 = gld<f32x4>(bias + co0);
       f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1, k1 = s1, k0 = s1;
-      // dense rows: (window, step, key) of the lane's row tiles are recomputed per channel tile (a few
-      // full-rate VALU ops each) instead of being kept in NRT registers beside the accumulators
+      // dense rows: row, address and mask word of the lane's row tiles are re-derived per channel tile (an
+      // add or an LDS read each) instead of being kept in NRT registers beside the accumulators
       int mo = m;
       if constexpr (DENSE) asm volatile("" : "+v"(mo));
+      const int rel0 = rt0 * 16 + mo;  // the lane's row of the wave's first row tile
+      const unsigned* ek = ektab + (tile & 1) * kRows + rel0;
+      float* orow = DENSE ? A.out + (((long long)g * A.n_win * kL + w0 + rel0) * COUT + co0) : nullptr;
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt) {
-        int t, w, sl = 0;
+        int t = 0, w = 0;
         bool valid;
         if constexpr (DENSE) {
-          const int dl = off + (rt0 + rt) * 16 + mo;
-          sl = dense::slot_of(dl), w = wf + sl, t = dl - sl * kL, valid = w < A.n_win;
+          valid = rel0 + rt * 16 < rows_left;
         } else {
           const int s = (rt0 + rt) >> 2;
           t = (((rt0 + rt) & 3) << 4) + m, w = w0 + s, valid = t < kL && w < A.n_win;
@@ -530,12 +601,14 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
         acc[ct][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
         bool keep[4] = {true, true, true, true};
         if (drop) {
-          unsigned key = skeys[DENSE ? 0 : rt >> 2];
+          // the row's mask word: dropout_bits2(key, t, co0) and (key, t, co0 + 2) are one xor and mix32 each
+          unsigned b01, b23;
           if constexpr (DENSE) {
-#pragma unroll
-            for (int q = 1; q < NKEY; ++q) key = sl == q ? skeys[q] : key;
+            const unsigned kt = ek[rt * 16];
+            b01 = mix32(kt ^ ((unsigned)co0 >> 1)), b23 = mix32(kt ^ (((unsigned)co0 >> 1) + 1u));
+          } else {
+            b01 = dropout_bits2(skeys[rt >> 2], t, co0), b23 = dropout_bits2(skeys[rt >> 2], t, co0 + 2);
           }
-          const unsigned b01 = dropout_bits2(key, t, co0), b23 = dropout_bits2(key, t, co0 + 2);
           keep[0] = (b01 & 0xFFFFu) >= A.thr_out;
           keep[1] = (b01 >> 16) >= A.thr_out;
           keep[2] = (b23 & 0xFFFFu) >= A.thr_out;
@@ -559,7 +632,10 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
 #pragma unroll
               for (int e = 0; e < 4; ++e) o[e] = keep[e] ? r[e] : __builtin_copysignf(r[e], -1.f);
             }
-            *reinterpret_cast<f32x4*>(A.out + (sample * kL + t) * COUT + co0) = o;
+            if constexpr (DENSE)
+              *reinterpret_cast<f32x4*>(orow + rt * 16 * COUT) = o;
+            else
+              *reinterpret_cast<f32x4*>(A.out + (sample * kL + t) * COUT + co0) = o;
           }
         }
         if constexpr (LAST) {
@@ -606,7 +682,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     __syncthreads();
     if (A.stats != nullptr) {
       double* dst = A.stats + ((long long)g * kStatSlots + slot) * 2 * COUT;
-      for (int i = tid; i < 2 * COUT; i += kThreads) {
+      // (dense rows: rare, so nothing of it is kept in registers across the tile loop)
+      for (int i = DENSE ? opaque_tid() : tid; i < 2 * COUT; i += kThreads) {
         atomicAdd(dst + i, st[i]);
         st[i] = 0.0;
       }
@@ -618,6 +695,10 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   //   iteration it: compute chunk it from buf[it & 1]; staging waves write chunk it+1 (loaded into
   //   registers one iteration earlier) into buf[(it+1) & 1] mid-way; barrier; issue the loads of it+2.
   // buf[(it+1) & 1] was last read by compute(it-1), which every wave finished before barrier(it-1).
+  for (int i = tid; i < 2 * kBufB / 16; i += kThreads) reinterpret_cast<f32x4*>(smem)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = tid; i < 2 * COUT; i += kThreads) st[i] = 0.0;
+  if (DENSE && stager) write_tables(t_begin);
+  __syncthreads();
   const int total = (t_end - t_begin) * NCH;
   auto chunk_tile = [&](int it) { return t_begin + it / NCH; };
   // dense rows: the tile's start inside its first window
@@ -888,7 +969,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs A) {
 // ------------------------------------------------------------------------------- launch helpers
 template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS, bool DENSE = false>
 hipError_t launch_layer(const LayerArgs& A, int grid, hipStream_t stream) {
-  constexpr int lds = lds_bytes(S, COUT, CK, DENSE);
+  constexpr int lds = lds_bytes(S, COUT, CK, KS, DENSE);
   static_assert(WPC * lds <= 160 * 1024, "LDS of the workgroups sharing a CU");
   auto k = layer_kernel<CIN, COUT, KS, S, WM, WN, LAST, LW, CK, WPC, PS, DENSE>;
   static bool attr = false;
@@ -946,7 +1027,7 @@ hipError_t launch_dense(const LayerArgs& A, int grid, hipStream_t stream) {
 
 int x3_lds_bytes(int layer) {
 #define APNEAUQ_X3_LDS(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
-  if (layer == L) return x3::lds_bytes(S, CO, CK);
+  if (layer == L) return x3::lds_bytes(S, CO, CK, K);
   APNEAUQ_X3_LAYERS(APNEAUQ_X3_LDS)
 #undef APNEAUQ_X3_LDS
   return 0;
