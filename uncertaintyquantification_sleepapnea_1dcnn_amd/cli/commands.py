@@ -25,6 +25,7 @@
 | analyze_calibration | (new) calibration + selective prediction with bootstrap CIs from a detail CSV |
 | analyze_patient_severity | (new) per-patient apnea index, severity and cohort metrics with patient-cluster bootstrap CIs |
 | analyze_pass_convergence | (new) how many passes / members are enough: every metric against the count, with bands over random subsets, from one raw prediction dump |
+| analyze_discrimination | (new) ROC / PR AUC and Mann-Whitney U (apnea vs normal, wrong vs right predictions) with window or patient-cluster bootstrap CIs, and the paired comparison of two detail CSVs |
 """
 from __future__ import annotations
 
@@ -425,6 +426,62 @@ def analyze_pass_convergence(argv=None):
     out_csv = os.path.join(a.output_dir, f"convergence_{a.method}.csv")
     convergence_from_predictions(pu, yu, pb, yb, counts, out_csv, n_orders=a.n_orders, seed=a.seed)
     print(f"Saved the curves to: {os.path.join(a.output_dir, f'convergence_{label}.csv')} and {out_csv}")
+    return table
+
+
+def analyze_discrimination(argv=None):
+    ap = argparse.ArgumentParser(description="ROC / PR AUC and Mann-Whitney U of a per-window detail CSV with bootstrap CIs: "
+                                             "apnea against normal windows (Predicted_Probability) and wrong against "
+                                             "right predictions (an uncertainty column).")
+    ap.add_argument("--input_csv", type=str, default="./detail_patient_DE.csv")
+    ap.add_argument("--score", choices=["Predictive_Entropy", "Predictive_Variance"], default="Predictive_Entropy",
+                    help="uncertainty column ranked against 'prediction wrong'")
+    ap.add_argument("--cluster", action="store_true", help="resample patients (Patient_ID) instead of windows")
+    ap.add_argument("--compare_csv", type=str, default=None,
+                    help="detail CSV of a second method over the same windows: paired differences input - compare")
+    ap.add_argument("--n_bootstrap", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--no_parity", action="store_true", help="draw with the device counter hash")
+    ap.add_argument("--output_plot_dir", type=str, default="./uq_plots/discrimination")
+    ap.add_argument("--output_csv", type=str, default="./discrimination_metrics.csv")
+    ap.add_argument("--no_plots", action="store_true")
+    a = ap.parse_args(argv)
+    import pandas as pd
+
+    from ..uq import discrimination as D
+
+    df = pd.read_csv(a.input_csv)
+    label = os.path.splitext(os.path.basename(a.input_csv))[0]
+    pids = df["Patient_ID"].to_numpy() if a.cluster else None
+    y = df["True_Label"].to_numpy()
+    common = dict(n_bootstrap=a.n_bootstrap, random_state=a.seed, parity=not a.no_parity, patient_ids=pids)
+    res = D.evaluate_discrimination(df["Predicted_Probability"].to_numpy(np.float32), y, label,
+                                    score=df[a.score].to_numpy(), output_plot_dir=a.output_plot_dir,
+                                    make_plots=not a.no_plots, **common)
+    ends = ("_mean", "_ci_lower", "_ci_upper")
+    rows = [{"metric": k, "value": v, "mean": res.get(k + "_mean", np.nan), "ci_lower": res.get(k + "_ci_lower", np.nan),
+             "ci_upper": res.get(k + "_ci_upper", np.nan)} for k, v in res.items() if not k.endswith(ends)]
+    if a.compare_csv:
+        other = pd.read_csv(a.compare_csv)
+        if len(other) != len(df) or not np.array_equal(other["True_Label"].to_numpy(), y):
+            raise ValueError(f"{a.compare_csv} does not hold the windows of {a.input_csv}")
+        cmp = D.compare_discrimination(df["Predicted_Probability"].to_numpy(np.float32),
+                                       other["Predicted_Probability"].to_numpy(np.float32), y,
+                                       score=df[a.score].to_numpy(), score_b=other[a.score].to_numpy(), **common)
+        for task in D.TASKS:
+            for m in D.METRICS:
+                k = f"{task}_{m}"
+                rows.append({"metric": k + "_diff", "value": cmp[k + "_diff"], "mean": cmp.get(k + "_diff_mean", np.nan),
+                             "ci_lower": cmp.get(k + "_diff_ci_lower", np.nan),
+                             "ci_upper": cmp.get(k + "_diff_ci_upper", np.nan)})
+                rows.append({"metric": k + "_share_a_gt_b", "value": cmp.get(k + "_share_a_gt_b", np.nan), "mean": np.nan,
+                             "ci_lower": np.nan, "ci_upper": np.nan})
+    table = pd.DataFrame(rows, columns=["metric", "value", "mean", "ci_lower", "ci_upper"])
+    print(f"{'patient-cluster' if a.cluster else 'window'} bootstrap, {a.n_bootstrap} replicates")
+    print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
+    if a.output_csv:
+        os.makedirs(os.path.dirname(os.path.abspath(a.output_csv)), exist_ok=True)
+        table.to_csv(a.output_csv, index=False)
     return table
 
 

@@ -43,6 +43,13 @@ hipError_t launch_patient_reduce(const float* probs, const float* m, const int* 
                                  int n_pat, int* pass_pos, long long* rec, hipStream_t stream);
 hipError_t launch_patient_bootstrap(const long long* prec, const int* idx, unsigned seed, int n_pat, int n_boot,
                                     long long* out, hipStream_t stream);
+int rank_max_splits();
+hipError_t launch_rank_count(const int* pos, const int* idx, unsigned seed, int n_draw, int n_sorted, int b0, int n_boot,
+                             long long stride, int* w, hipStream_t stream);
+hipError_t launch_rank_totals(const int* w, long long stride, const unsigned char* packed, const int* bounds, int n,
+                              int n_boot, int splits, long long* tot, hipStream_t stream);
+hipError_t launch_rank_scan(const int* w, long long stride, const unsigned char* packed, const int* bounds,
+                            const long long* tot, int n, int n_boot, int splits, long long* part, hipStream_t stream);
 hipError_t launch_converge(const float* probs, const int* y, const int* orders, const int* counts, int t_count, int n,
                            int n_rep, int n_cnt, int rep_groups, long long* out, hipStream_t stream);
 int zero_max_buffers();
@@ -423,6 +430,84 @@ at::Tensor patient_bootstrap(const at::Tensor& prec, const c10::optional<at::Ten
                                           (int)n_pat, (int)n_boot, reinterpret_cast<long long*>(out.data_ptr<int64_t>()),
                                           cur_stream()),
         "patient_bootstrap");
+  return out;
+}
+
+// Rank statistics (uq_rank.hip).  rank_count: (B, n_sorted) int32 multiplicities of the sorted windows in replicates
+// b0 .. b0 + B - 1, rows 16-B aligned (the result is a view of a (B, n_sorted rounded up to 4) buffer).  Limits:
+// at most 2^27 draws per replicate, so a replicate's total weight stays below 2^31.
+at::Tensor rank_count(const at::Tensor& pos, const c10::optional<at::Tensor>& idx, int64_t seed, int64_t b0,
+                      int64_t n_boot, int64_t n_sorted) {
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.dim() == 1,
+              "rank_count: pos must be (n,) int32 on the GPU");
+  const int64_t n_draw = pos.size(0);
+  TORCH_CHECK(n_draw >= 1 && n_draw <= (int64_t(1) << 27), "rank_count: n must be in 1..2^27");
+  TORCH_CHECK(n_sorted >= 1 && n_sorted <= n_draw, "rank_count: n_sorted must be in 1..n");
+  TORCH_CHECK(n_boot >= 0 && b0 >= 0 && b0 + n_boot < (int64_t(1) << 31), "rank_count: bad replicate range");
+  auto pp = pos.contiguous();
+  const int* ip = nullptr;
+  at::Tensor ii;
+  if (idx.has_value()) {
+    ii = idx->to(at::kInt).contiguous();
+    TORCH_CHECK(ii.is_cuda() && ii.dim() == 2 && ii.size(0) == n_boot && ii.size(1) == n_draw,
+                "rank_count: idx must be (B, n) on the GPU");
+    ip = ii.data_ptr<int>();
+  }
+  const int64_t stride = (n_sorted + 3) / 4 * 4;
+  const at::DeviceGuard guard(pp.device());
+  auto w = at::zeros({n_boot, stride}, pp.options());
+  check(apneauq::launch_rank_count(pp.data_ptr<int>(), ip, (unsigned)seed, (int)n_draw, (int)n_sorted, (int)b0,
+                                   (int)n_boot, (long long)stride, w.data_ptr<int>(), cur_stream()),
+        "rank_count");
+  return w.narrow(1, 0, n_sorted);
+}
+
+// rank_scan: (B, 6) int64 sums W, P, U2, groups, prauc_q, ap_q of weight rows over the sorted windows.  bounds
+// (G + 1,) are the split points (tie-group starts, ops/rank.py:split_bounds); the result does not depend on G.
+// Limits: n <= 2^27, G <= 64, weights non-negative with every row's total below 2^31 (checked on the totals).
+at::Tensor rank_scan(const at::Tensor& w, const at::Tensor& packed, const at::Tensor& bounds) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kInt && w.dim() == 2, "rank_scan: w must be (B, n) int32 on the GPU");
+  const int64_t n_boot = w.size(0), n = w.size(1);
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 27), "rank_scan: n must be in 1..2^27");
+  TORCH_CHECK(n_boot >= 0 && n_boot < (int64_t(1) << 31), "rank_scan: bad number of replicates");
+  TORCH_CHECK(packed.is_cuda() && packed.scalar_type() == at::kByte && packed.dim() == 1 && packed.size(0) == n,
+              "rank_scan: packed must be (n,) uint8 on the GPU");
+  TORCH_CHECK(bounds.is_cuda() && bounds.scalar_type() == at::kInt && bounds.dim() == 1 && bounds.size(0) >= 2 &&
+                  bounds.size(0) <= apneauq::rank_max_splits() + 1,
+              "rank_scan: bounds must be (G + 1,) int32 on the GPU, G in 1..64");
+  const int64_t splits = bounds.size(0) - 1;
+  const at::DeviceGuard guard(w.device());
+  // rows on 16-B boundaries for the vector loads: the view rank_count returns qualifies, anything else is copied
+  at::Tensor ww = w;
+  const int64_t stride = (n + 3) / 4 * 4;
+  if (n_boot > 0 && (w.stride(1) != 1 || w.stride(0) % 4 != 0 || w.stride(0) < n ||
+                     reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 != 0)) {
+    auto buf = at::zeros({n_boot, stride}, w.options());
+    buf.narrow(1, 0, n).copy_(w);
+    ww = buf.narrow(1, 0, n);
+  }
+  auto pk = packed.contiguous(), bb = bounds.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pk.data_ptr()) % 4 == 0, "rank_scan: 4-B alignment of packed required");
+  auto tot = at::empty({n_boot, splits, 3}, w.options().dtype(at::kLong));
+  auto part = at::empty({n_boot, splits, 4}, w.options().dtype(at::kLong));
+  auto out = at::empty({n_boot, 6}, w.options().dtype(at::kLong));
+  if (n_boot == 0) return out;
+  const long long row = n_boot > 1 ? ww.stride(0) : stride;
+  check(apneauq::launch_rank_totals(ww.data_ptr<int>(), row, pk.data_ptr<uint8_t>(), bb.data_ptr<int>(), (int)n,
+                                    (int)n_boot, (int)splits, reinterpret_cast<long long*>(tot.data_ptr<int64_t>()),
+                                    cur_stream()),
+        "rank_totals");
+  auto t = tot.sum(1);  // (B, 3): positives, negatives, negative weights
+  TORCH_CHECK(t.select(1, 2).max().item<int64_t>() == 0, "rank_scan: weights must be non-negative");
+  auto total = t.select(1, 0) + t.select(1, 1);
+  TORCH_CHECK(total.max().item<int64_t>() < (int64_t(1) << 31), "rank_scan: a replicate's total weight must stay below 2^31");
+  check(apneauq::launch_rank_scan(ww.data_ptr<int>(), row, pk.data_ptr<uint8_t>(), bb.data_ptr<int>(),
+                                  reinterpret_cast<const long long*>(tot.data_ptr<int64_t>()), (int)n, (int)n_boot,
+                                  (int)splits, reinterpret_cast<long long*>(part.data_ptr<int64_t>()), cur_stream()),
+        "rank_scan");
+  out.select(1, 0).copy_(total);
+  out.select(1, 1).copy_(t.select(1, 0));
+  out.narrow(1, 2, 4).copy_(part.sum(1));
   return out;
 }
 
@@ -1335,6 +1420,8 @@ TORCH_LIBRARY(apneauq, m) {
   m.def("calib_bootstrap(Tensor rec, Tensor? idx, int seed, int n_boot, int n_global, int lo, int n_bins, int n_thr, int slices) -> Tensor");
   m.def("patient_reduce(Tensor probs, Tensor m, Tensor y, Tensor code, int n_pat) -> (Tensor, Tensor)");
   m.def("patient_bootstrap(Tensor prec, Tensor? idx, int seed, int n_boot) -> Tensor");
+  m.def("rank_count(Tensor pos, Tensor? idx, int seed, int b0, int n_boot, int n_sorted) -> Tensor");
+  m.def("rank_scan(Tensor w, Tensor packed, Tensor bounds) -> Tensor");
   m.def("converge(Tensor probs, Tensor y, Tensor orders, Tensor counts, int rep_groups) -> Tensor");
   m.def("fused_layout() -> int[]", &fused_layout);
   m.def("fused_layout_x3() -> int[]", &fused_layout_x3);
@@ -1401,6 +1488,8 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("calib_bootstrap", &calib_bootstrap);
   m.impl("patient_reduce", &patient_reduce);
   m.impl("patient_bootstrap", &patient_bootstrap);
+  m.impl("rank_count", &rank_count);
+  m.impl("rank_scan", &rank_scan);
   m.impl("converge", &converge);
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_multi", &adam_step_multi);
