@@ -10,7 +10,8 @@
 //   counts[1 + nb .. 2 nb]    negatives per bucket                      (nb = n_thr + 1)
 //
 // The bucket is a lower_bound over the fp32 threshold table staged in LDS, so it equals
-// torch.bucketize(p, thr) bit for bit; per-block LDS histograms are flushed with one 64-bit
+// torch.bucketize(p, thr) bit for bit -- a NaN prediction included, which compares below nothing and
+// lands in the last bucket (and counts as "not > 0.5" for the accuracy); per-block LDS histograms are flushed with one 64-bit
 // atomic per non-empty bin.
 #include "common.h"
 
@@ -34,10 +35,10 @@ __global__ __launch_bounds__(256) void update_kernel(const float* p, const float
     const float pi = p[i];
     const bool pos = y[i] > 0.5f;
     mine += ((pi > 0.5f) == pos) ? 1u : 0u;
-    int lo = 0, hi = n_thr;  // first index with t[idx] >= pi
+    int lo = 0, hi = n_thr;  // first index with t[idx] >= pi; n_thr for NaN, like torch.bucketize
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (t[mid] < pi)
+      if (!(t[mid] >= pi))
         lo = mid + 1;
       else
         hi = mid;

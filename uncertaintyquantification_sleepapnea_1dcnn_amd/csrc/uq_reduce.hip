@@ -4,7 +4,10 @@
 //            variance, H(E[p]) and E[H(p)] in nats with the SciPy clip to [1e-10, 1-1e-10],
 //            MI = max(H - E[H], 0)) plus the per-window CSV columns of
 //            analyze_mcd_patient_level.py:107-117 (entropy in BITS with log2(p + 1e-9), label p>0.5).
-//            One thread per window, one pass over the T (or M) samples, fp32 like the reference.
+//            One thread per window; fp32 entropies like the reference, the sums over the T (or M)
+//            samples in fp64.
+//            A window with a non-finite probability in any pass has NaN in rows MEAN..ENT_BITS and
+//            LABEL 0 (np.clip and scipy.stats.entropy hand a NaN through; fmaxf / fminf would not).
 // bootstrap  replaces uq_techniques.py:137-157, which re-runs the whole metric computation for
 //            each of B resamples.  The per-window metrics do not change under resampling, so every
 //            replicate is a gather + masked mean; one workgroup per replicate, fp64 accumulation.
@@ -15,7 +18,10 @@ namespace apneauq {
 // metric rows written by uq_reduce (out[k * n + i])
 enum UqRow { kMean = 0, kVar, kEntNats, kExpEnt, kMI, kEntBits, kLabel, kUqRows };
 
-__device__ __forceinline__ float bin_entropy_nats(float p) {
+// One compiled body for H(mean) and for the H(p) inside E[H] (noinline): inlined, the two sites are
+// contracted into different fma chains and round differently, and T = 1 gets MI = one ulp of H where
+// it is exactly 0.
+__device__ __noinline__ float bin_entropy_nats(float p) {
   // scipy.stats.entropy([1-p, p]) after np.clip(., 1e-10, 1-1e-10) in float32 (the upper bound
   // rounds to 1.0f), including SciPy's renormalisation by the sum.
   float q = 1.0f - p;
@@ -31,22 +37,33 @@ __global__ __launch_bounds__(256) void uq_reduce_kernel(const float* __restrict_
                                                          float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float s = 0.f, eh = 0.f;
+  // The sums over T run in fp64 (T adds per window, nothing next to the logarithms): a sequential fp32
+  // sum of T values near 1 loses the last bits of the mean, and H(mean) is steepest exactly there.
+  double s = 0.0, eh = 0.0;
+  bool finite = true;
   for (int t = 0; t < t_count; ++t) {
     const float p = probs[(long long)t * n + i];
-    s += p;
-    eh += bin_entropy_nats(p);
+    finite = finite && fabsf(p) <= 3.402823466e+38f;  // false for NaN and +-inf
+    s += (double)p;
+    eh += (double)bin_entropy_nats(p);
   }
-  const float mean = s / (float)t_count;
-  float v = 0.f;
+  const double mean_d = s / (double)t_count;
+  const float mean = (float)mean_d;
+  double v = 0.0;
   for (int t = 0; t < t_count; ++t) {
-    const float d = probs[(long long)t * n + i] - mean;
+    const double d = (double)probs[(long long)t * n + i] - mean_d;
     v += d * d;
   }
-  const float var = v / (float)t_count;
+  const float var = (float)(v / (double)t_count);
   const float h = bin_entropy_nats(mean);
-  const float e = eh / (float)t_count;
+  const float e = (float)(eh / (double)t_count);
   const float bits = -(mean * log2f(mean + 1e-9f) + (1.0f - mean) * log2f(1.0f - mean + 1e-9f));
+  if (!finite) {
+    const float nan = __builtin_nanf("");
+    for (int k = kMean; k <= kEntBits; ++k) out[k * (long long)n + i] = nan;
+    out[kLabel * (long long)n + i] = 0.f;
+    return;
+  }
   out[kMean * (long long)n + i] = mean;
   out[kVar * (long long)n + i] = var;
   out[kEntNats * (long long)n + i] = h;

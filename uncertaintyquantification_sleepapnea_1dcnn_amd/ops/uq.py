@@ -34,7 +34,11 @@ def metrics_eager(probs: torch.Tensor) -> torch.Tensor:
     h = _bin_entropy_nats_t(mean)
     e = _bin_entropy_nats_t(p).mean(0)
     bits = -(mean * torch.log2(mean + 1e-9) + (1 - mean) * torch.log2(1 - mean + 1e-9))
-    return torch.stack([mean, var, h, e, (h - e).clamp_min(0), bits, (mean > 0.5).float()])
+    out = torch.stack([mean, var, h, e, (h - e).clamp_min(0), bits, (mean > 0.5).float()])
+    bad = ~torch.isfinite(p).all(0)  # a non-finite probability in any pass: NaN rows, LABEL 0 (the kernel's rule)
+    out[:LABEL, bad] = float("nan")
+    out[LABEL, bad] = 0.0
+    return out
 
 
 def metrics(probs: torch.Tensor) -> torch.Tensor:

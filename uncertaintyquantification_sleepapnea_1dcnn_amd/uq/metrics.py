@@ -24,15 +24,16 @@ AGG_KEYS = (
 
 
 def binary_entropy_nats(p: np.ndarray, epsilon: float = 1e-10) -> np.ndarray:
-    """H([1-p, p]) in nats with SciPy semantics: clip, renormalise, -sum x log x (dtype kept)."""
+    """H([1-p, p]) in nats with SciPy semantics: clip, renormalise, -sum x log x (dtype kept).
+    A NaN probability gives NaN, as ``np.clip`` and ``scipy.stats.entropy`` do."""
     p = np.asarray(p)
     q = 1 - p
     pc = np.clip(p, epsilon, 1 - epsilon)
     qc = np.clip(q, epsilon, 1 - epsilon)
     s = pc + qc
     pc, qc = pc / s, qc / s
-    with np.errstate(divide="ignore", invalid="ignore"):
-        h = -(np.where(pc > 0, pc * np.log(pc), 0) + np.where(qc > 0, qc * np.log(qc), 0))
+    with np.errstate(invalid="ignore"):
+        h = -(pc * np.log(pc) + qc * np.log(qc))
     return h.astype(p.dtype if np.issubdtype(p.dtype, np.floating) else np.float64)
 
 
@@ -60,6 +61,9 @@ def per_window(predictions: np.ndarray) -> Dict[str, np.ndarray]:
     total = binary_entropy_nats(mean)
     expected = np.mean(np.stack([binary_entropy_nats(pt) for pt in p]), axis=0)
     mi = np.maximum(total - expected, 0)
+    bad = ~np.isfinite(p).all(axis=0)
+    if bad.any():  # a non-finite probability in any pass: every quantity of the window is NaN (inf too)
+        mean, var, total, expected, mi = (np.where(bad, np.nan, a).astype(a.dtype) for a in (mean, var, total, expected, mi))
     return {"mean_pred": mean, "pred_variance": var, "total_pred_entropy": total,
             "expected_aleatoric_entropy": expected, "mutual_info": mi}
 
