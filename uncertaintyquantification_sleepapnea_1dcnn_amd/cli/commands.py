@@ -25,6 +25,7 @@
 | analyze_calibration | (new) calibration + selective prediction with bootstrap CIs from a detail CSV |
 | analyze_patient_severity | (new) per-patient apnea index, severity and cohort metrics with patient-cluster bootstrap CIs |
 | analyze_pass_convergence | (new) how many passes / members are enough: every metric against the count, with bands over random subsets, from one raw prediction dump |
+| analyze_laplace_patient_level | (new) last-layer Laplace UQ evaluation with per-window results: fits (or loads) the posterior of the Dense head, then the outputs of analyze_mcd_patient_level |
 | analyze_discrimination | (new) ROC / PR AUC and Mann-Whitney U (apnea vs normal, wrong vs right predictions) with window or patient-cluster bootstrap CIs, and the paired comparison of two detail CSVs |
 """
 from __future__ import annotations
@@ -142,6 +143,60 @@ def analyze_mcd_patient_level(argv=None, global_mode: bool = False):
 
 def evaluate_mcd_global(argv=None):
     return analyze_mcd_patient_level(argv, global_mode=True)
+
+
+def _load_named(data_dir, name, mmap=False):
+    """A ``.npy`` given as a path, or as a processed-dataset name under ``data_dir`` (FILE_ALIASES honoured)."""
+    from ..data.prepare import load_processed
+
+    if os.path.exists(name):
+        return np.load(name, mmap_mode="r" if mmap else None, allow_pickle=False)
+    return load_processed(data_dir, name, mmap=mmap)
+
+
+def analyze_laplace_patient_level(argv=None):
+    ap = argparse.ArgumentParser(description="Last-layer Laplace UQ evaluation with per-window results: one trained "
+                                             "model, one deterministic pass, draws of the Dense head.")
+    _uq_common(ap)
+    ap.add_argument("--model_path", type=str, default="./AlCNN1D_no_pool.keras")
+    ap.add_argument("--fit_x", type=str, default="X_train_win_std_smote.npy",
+                    help="training windows (.npy path, or a processed-dataset name under --data_dir)")
+    ap.add_argument("--fit_y", type=str, default="y_train_smote.npy", help="training labels (as --fit_x)")
+    ap.add_argument("--prior_precision", type=str, default="auto", help="'auto' (evidence maximisation) or a float")
+    ap.add_argument("--n_samples", type=int, default=50)
+    ap.add_argument("--state", type=str, default="./laplace_state.npz",
+                    help="posterior file: loaded if present, else fitted on --fit_x / --fit_y and saved")
+    ap.add_argument("--output_plot_dir", type=str, default="./uq_plots_patient/laplace_no_pool")
+    ap.add_argument("--output_csv_dir", type=str, default="./uq_results_patient_laplace")
+    a = ap.parse_args(argv)
+    from ..models.cnn import load_model
+    from ..uq.drivers import evaluate_laplace
+    from ..uq.laplace import LaplaceState, fit_laplace
+
+    np.random.seed(a.seed)
+    prior = a.prior_precision if a.prior_precision == "auto" else float(a.prior_precision)
+    Xu, yu, pids, Xr, yr = _load_test(a.data_dir)
+    model = load_model(a.model_path)
+    det = model.predict(Xu)
+    print(f"Deterministic Accuracy (training=False) on Unbalanced Set: {np.mean((det.ravel() > 0.5) == yu):.4f}")
+    if os.path.exists(a.state):
+        state = LaplaceState.load(a.state)
+        print(f"Loaded the Laplace posterior from {a.state} (prior precision {state.prior_precision:.6g})")
+    else:
+        state = fit_laplace(model, _load_named(a.data_dir, a.fit_x, mmap=True), _load_named(a.data_dir, a.fit_y), prior)
+        d = os.path.dirname(a.state)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        print(f"Fitted the Laplace posterior on {state.n_valid} of {state.n_total} windows (prior precision "
+              f"{state.prior_precision:.6g}, log evidence {state.log_evidence:.4f}); saved to {state.save(a.state)}")
+    res = {}
+    res["unbalanced"] = evaluate_laplace(model, state, Xu, yu, pids, "CNN_LLLA_Unbalanced", True, a.n_samples,
+                                         a.n_bootstrap, a.seed, a.output_csv_dir, a.output_plot_dir,
+                                         make_plots=not a.no_plots)
+    res["balanced"] = evaluate_laplace(model, state, Xr, yr, None, "CNN_LLLA_Balanced_RUS", False, a.n_samples,
+                                       a.n_bootstrap, a.seed, a.output_csv_dir, a.output_plot_dir, raw_pred_path="",
+                                       make_plots=not a.no_plots)
+    return res
 
 
 def analyze_de_patient_level(argv=None):

@@ -50,6 +50,12 @@ hipError_t launch_rank_totals(const int* w, long long stride, const unsigned cha
                               int n_boot, int splits, long long* tot, hipStream_t stream);
 hipError_t launch_rank_scan(const int* w, long long stride, const unsigned char* packed, const int* bounds,
                             const long long* tot, int n, int n_boot, int splits, long long* part, hipStream_t stream);
+int laplace_max_dp();
+long long laplace_part_doubles(int D);
+hipError_t launch_laplace_gram(const float* phi, const double* theta, const unsigned char* y, long long n, int D,
+                               long long range_len, int grid, double* part, double* out, hipStream_t stream);
+hipError_t launch_laplace_predict(const float* phi, const double* mx, long long n, int D, int T, float* preds,
+                                  double* mu, double* vv, double* probit, hipStream_t stream);
 hipError_t launch_converge(const float* probs, const int* y, const int* orders, const int* counts, int t_count, int n,
                            int n_rep, int n_cnt, int rep_groups, long long* out, hipStream_t stream);
 int zero_max_buffers();
@@ -509,6 +515,58 @@ at::Tensor rank_scan(const at::Tensor& w, const at::Tensor& packed, const at::Te
   out.select(1, 1).copy_(t.select(1, 0));
   out.narrow(1, 2, 4).copy_(part.sum(1));
   return out;
+}
+
+// Last-layer Laplace (uq_laplace.hip).  laplace_gram: flat fp64 [(D+1)^2 H | (D+1) g | loglik | n_valid] of phi (n, D)
+// fp32, theta (D+1) fp64 and y (n) uint8.  range_len (windows per range, ops/laplace.py:range_len) fixes the order of
+// the fp64 additions; grid (0: one workgroup per range) does not change the result.  Limits: D + 1 <= 128 and the
+// range partials stay within 64 MB.
+at::Tensor laplace_gram(const at::Tensor& phi, const at::Tensor& theta, const at::Tensor& y, int64_t range_len,
+                        int64_t grid) {
+  TORCH_CHECK(phi.is_cuda() && phi.scalar_type() == at::kFloat && phi.dim() == 2,
+              "laplace_gram: phi must be (n, D) fp32 on the GPU");
+  const int64_t n = phi.size(0), D = phi.size(1);
+  TORCH_CHECK(D >= 1 && D + 1 <= apneauq::laplace_max_dp(), "laplace_gram: D + 1 must be in 2..128");
+  TORCH_CHECK(theta.is_cuda() && theta.scalar_type() == at::kDouble && theta.dim() == 1 && theta.size(0) == D + 1,
+              "laplace_gram: theta must be (D + 1,) fp64 on the GPU");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kByte && y.dim() == 1 && y.size(0) == n,
+              "laplace_gram: y must be (n,) uint8 on the GPU");
+  TORCH_CHECK(range_len >= 1 && grid >= 0 && grid < (int64_t(1) << 20), "laplace_gram: bad range_len / grid");
+  const int64_t n_ranges = (n + range_len - 1) / range_len;
+  const int64_t pd = apneauq::laplace_part_doubles((int)D);
+  TORCH_CHECK(n_ranges * pd * 8 <= (int64_t(64) << 20), "laplace_gram: the range partials must stay within 64 MB");
+  auto pp = phi.contiguous(), tt = theta.contiguous(), yy = y.contiguous();
+  const at::DeviceGuard guard(pp.device());
+  auto part = at::empty({std::max<int64_t>(n_ranges, 1) * pd}, tt.options());
+  auto out = at::empty({(D + 1) * (D + 1) + (D + 1) + 2}, tt.options());
+  check(apneauq::launch_laplace_gram(pp.data_ptr<float>(), tt.data_ptr<double>(), yy.data_ptr<uint8_t>(), (long long)n,
+                                     (int)D, (long long)range_len, (int)grid, part.data_ptr<double>(),
+                                     out.data_ptr<double>(), cur_stream()),
+        "laplace_gram");
+  return out;
+}
+
+// laplace_predict: mx (D+1, 1 + T + D+1) fp64 = [theta | theta_1 .. theta_T | L] -> preds (T, n) fp32 and the moments
+// (3, n) fp64: mean logit, logit variance, probit probability.  NaN for a window with a non-finite feature.
+std::tuple<at::Tensor, at::Tensor> laplace_predict(const at::Tensor& phi, const at::Tensor& mx, int64_t T) {
+  TORCH_CHECK(phi.is_cuda() && phi.scalar_type() == at::kFloat && phi.dim() == 2,
+              "laplace_predict: phi must be (n, D) fp32 on the GPU");
+  const int64_t n = phi.size(0), D = phi.size(1);
+  TORCH_CHECK(D >= 1 && D + 1 <= apneauq::laplace_max_dp(), "laplace_predict: D + 1 must be in 2..128");
+  TORCH_CHECK(T >= 0 && T < (int64_t(1) << 24), "laplace_predict: T must be in 0..2^24");
+  TORCH_CHECK(mx.is_cuda() && mx.scalar_type() == at::kDouble && mx.dim() == 2 && mx.size(0) == D + 1 &&
+                  mx.size(1) == T + D + 2,
+              "laplace_predict: mx must be (D + 1, T + D + 2) fp64 on the GPU");
+  auto pp = phi.contiguous(), mm = mx.contiguous();
+  const at::DeviceGuard guard(pp.device());
+  auto preds = at::empty({T, n}, pp.options());
+  auto mom = at::empty({3, n}, mm.options());
+  if (n == 0) return std::make_tuple(preds, mom);
+  double* mp = mom.data_ptr<double>();
+  check(apneauq::launch_laplace_predict(pp.data_ptr<float>(), mm.data_ptr<double>(), (long long)n, (int)D, (int)T,
+                                        preds.data_ptr<float>(), mp, mp + n, mp + 2 * n, cur_stream()),
+        "laplace_predict");
+  return std::make_tuple(preds, mom);
 }
 
 // Pass / member-count convergence (uq_converge.hip): (R, K, 11) int64 sums over the windows of the metrics of
@@ -1422,6 +1480,8 @@ TORCH_LIBRARY(apneauq, m) {
   m.def("patient_bootstrap(Tensor prec, Tensor? idx, int seed, int n_boot) -> Tensor");
   m.def("rank_count(Tensor pos, Tensor? idx, int seed, int b0, int n_boot, int n_sorted) -> Tensor");
   m.def("rank_scan(Tensor w, Tensor packed, Tensor bounds) -> Tensor");
+  m.def("laplace_gram(Tensor phi, Tensor theta, Tensor y, int range_len, int grid) -> Tensor");
+  m.def("laplace_predict(Tensor phi, Tensor mx, int T) -> (Tensor, Tensor)");
   m.def("converge(Tensor probs, Tensor y, Tensor orders, Tensor counts, int rep_groups) -> Tensor");
   m.def("fused_layout() -> int[]", &fused_layout);
   m.def("fused_layout_x3() -> int[]", &fused_layout_x3);
@@ -1490,6 +1550,8 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("patient_bootstrap", &patient_bootstrap);
   m.impl("rank_count", &rank_count);
   m.impl("rank_scan", &rank_scan);
+  m.impl("laplace_gram", &laplace_gram);
+  m.impl("laplace_predict", &laplace_predict);
   m.impl("converge", &converge);
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_multi", &adam_step_multi);

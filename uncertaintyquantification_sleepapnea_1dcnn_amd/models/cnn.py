@@ -311,6 +311,29 @@ class AlarconCNN1D:
             outs.append(torch.sigmoid(self.logits(x[s: s + step])).cpu().numpy())
         return np.concatenate(outs) if outs else np.zeros((0, 1), np.float32)
 
+    def last_layer_features(self, x, max_samples: Optional[int] = None) -> torch.Tensor:
+        """Penultimate features (N, C_last) fp32 on the model's device: the global average pool the Dense head
+        reads, inference mode (BN on the moving statistics, dropout off).
+
+        On the fp32-faithful engine (:meth:`uses_x3`) they come from the sums its head kernel reads
+        (``ops/x3.py:features_running``; ``max_samples`` bounds the windows per launch).  Everything else
+        -- other architectures, ``precision="bf16"`` models, the CPU -- runs the PyTorch reference forward
+        in fp32 on the model's device: correct, but slow (cuDNN-style convolutions, no HIP kernel)."""
+        x = self._as_input(x)
+        if self.uses_x3():
+            from ..ops import x3
+
+            _ext.require()
+            return x3.features_running(self.x3_model(), x, max_samples=max_samples)
+        outs = []
+        step = 4096
+        with torch.no_grad():
+            for s in range(0, x.shape[0], step):
+                outs.append(R.forward(self.spec, self.store.as_dict(), x[s: s + step], return_features=True).float())
+        if not outs:
+            return torch.empty(0, self.spec.final_channels, dtype=torch.float32, device=self.device)
+        return torch.cat(outs, dim=0)
+
     # ------------------------------------------------------------------ training
     def train_step(self, x, y, return_probs: bool = False, grad_allreduce=None, dp_step=None):
         """One optimizer step on a batch (Keras training semantics); returns the summed BCE."""

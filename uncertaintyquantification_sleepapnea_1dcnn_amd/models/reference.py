@@ -111,6 +111,7 @@ def forward(
     bn_stats_hook=None,
     dtype: Optional[torch.dtype] = None,
     relu_masks=None,
+    return_features: bool = False,
 ) -> torch.Tensor:
     """Forward pass; returns probabilities (N, 1) (or logits).
 
@@ -125,6 +126,8 @@ def forward(
     (one bool (N, L, C) tensor per block) replaces each ReLU's branch choice by the given pattern -- the
     oracle then differentiates the same piecewise-linear branch as an fp32 run whose pre-activations
     sat within rounding of zero (a flipped ReLU moves a gradient by a whole element, not by rounding).
+    ``return_features`` returns the penultimate features (N, C_last) -- the global average pool the Dense
+    head reads -- instead of the head's output.
     """
     use_drop = training if dropout is None else dropout
     use_batch = training if bn_batch_stats is None else bn_batch_stats
@@ -156,6 +159,8 @@ def forward(
             key = rng.stream_key(seed, i - 1, pass_id)
             h = rng.dropout_apply_torch(h, key, sample_ids, b.dropout)
     g = h.mean(dim=1)
+    if return_features:
+        return g
     logit = g @ p["output_layer/kernel"] + p["output_layer/bias"]
     return logit if return_logits else torch.sigmoid(logit)
 

@@ -11,7 +11,9 @@ tiles; BN apply, dropout, GAP, Dense and sigmoid are fp32.  Workloads:
   ``model(x, training=True)`` T times on the whole test set): per-pass batch statistics of every BN
   over all windows (SyncBN over ranks), dropout, the moving-average side effect;
 * :func:`forward_running` -- BN on moving statistics: Deep-Ensemble ``predict`` of M members
-  (``uq_techniques.py:29``) or standard MC Dropout (dropout on).
+  (``uq_techniques.py:29``) or standard MC Dropout (dropout on);
+* :func:`features_running` -- the penultimate features the head reads (dropout off), for the last-layer
+  Laplace approximation (``uq/laplace.py``).
 
 Weights are packed once per model set (:class:`X3Model`); activations live in HBM between the six
 layer launches (fp32 ReLU outputs; the dropout mask of block l is drawn from the counter hash by the
@@ -405,7 +407,9 @@ def forward_running(model: X3Model, x: torch.Tensor, n_pass: int = 1, dropout: b
 
 
 def _forward_running(model: X3Model, x: torch.Tensor, n_pass: int, dropout: bool, seed: int, pass_offset: int,
-                     window_offset: int, logits: bool) -> torch.Tensor:
+                     window_offset: int, logits: bool, features: bool = False) -> torch.Tensor:
+    """``features``: stop before the head and return (N, C_last) fp32 features of one model; with ``dropout``
+    off this runs the per-sample-prescale layer sequence below with every mask open."""
     spec, o = model.spec, _ops()
     n = x.shape[0]
     G = model.G
@@ -419,7 +423,7 @@ def _forward_running(model: X3Model, x: torch.Tensor, n_pass: int, dropout: bool
     dsc = [_dsc(b.dropout) if dropout else 1.0 for b in spec.blocks]
     eps, mom = float(spec.bn_epsilon), float(spec.bn_momentum)
     seed = int(seed) & ((1 << 63) - 1)
-    if not dropout:
+    if not dropout and not features:
         return _predict_members(model, ws, x, G, eps, mom, logits)
     sl = _sign_layers()
     # BN affine of the moving statistics, per member (shared by all passes with dropout)
@@ -438,6 +442,12 @@ def _forward_running(model: X3Model, x: torch.Tensor, n_pass: int, dropout: bool
                    CH[l + 1] if per_member else 0, ws.aff[l - 1], 2 * CH[l] if per_member else 0, None, n, groups,
                    dropout and l == 1, thr[l - 1], thr[l], seed, int(pass_offset),
                    int(window_offset), 0, ws.smax[l - 1], ws.amax[l - 1], sm, None, *_sign(l, sl))
+    if features:
+        if groups != 1:
+            raise ValueError("features of one model and one pass")
+        sums = ws.sums[: n * 2 * CH[6]].view(n, 2, CH[6])
+        aff = ws.aff[5][: 2 * CH[6]].view(2, CH[6])
+        return (aff[0] * sums[:, 0] + aff[1] * sums[:, 1]) / 60.0
     o.x3_head(ws.sums, ws.aff[5], 2 * CH[6] if per_member else 0, model.dw, model.db, CH[6] if per_member else 0,
               ws.out, n, groups, bool(logits))
     return ws.out[: groups * n].view(G, n_pass, n).clone()
@@ -485,6 +495,31 @@ def _predict_members(model: X3Model, ws: "_Workspace", x: torch.Tensor, G: int, 
     o.x3_head(ws.sums, ws.aff[5], 2 * CH[6] if per_member else 0, model.dw, model.db, CH[6] if per_member else 0,
               ws.out, n, G, bool(logits))
     return ws.out[: G * n].view(G, 1, n).clone()
+
+
+@torch.no_grad()
+def features_running(model: X3Model, x: torch.Tensor, max_samples: Optional[int] = None) -> torch.Tensor:
+    """Penultimate features (N, C_last) fp32 of one model: GAP of block 6 after BN on the moving statistics,
+    dropout off -- ``phi_c = (s_c S1_c + t_c S0_c) / 60`` from the sums the head kernel reads.  Window-chunked
+    like :func:`forward_running`.
+
+    The layer sequence is the one of the running-statistics MC Dropout path with every mask open (thresholds
+    0, scale 1), whose range-safe prescale is per sample: a window's features do not depend on the other
+    windows of its chunk, bitwise.  (The Deep-Ensemble sequence, :func:`_predict_members`, picks its prescale per
+    launch: its features moved by up to 6e-6 of their own value between chunkings where ``s S1`` and ``t S0``
+    cancel, 2e-7 of the largest feature.)  ``sigmoid(dense . phi + bias)`` agrees with
+    :func:`forward_running`'s probability to fp32 rounding of the head."""
+    if model.G != 1:
+        raise ValueError("features of one model")
+    x = x.to(device=model.device, dtype=torch.float32).contiguous()
+    n = x.shape[0]
+    if n == 0:
+        return torch.empty(0, CH[6], dtype=torch.float32, device=model.device)
+    if max_samples is None:
+        max_samples = _max_samples(model.device, BYTES_PER_SAMPLE + R1_BYTES)
+    wc = max(1, int(max_samples))
+    parts = [_forward_running(model, x[s: s + wc], 1, False, 0, 0, s, False, features=True) for s in range(0, n, wc)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
 
 def split_f16(a: torch.Tensor):

@@ -126,6 +126,29 @@ def evaluate_deep_ensemble(models: List, X, y, patient_ids=None, model_eval_labe
                    n_bootstrap, seed, raw_pred_path, make_plots)
 
 
+def evaluate_laplace(model, state, X, y, patient_ids=None, model_eval_label: str = "CNN_LLLA",
+                     save_detailed_csv: bool = False, n_samples: int = 50, n_bootstrap: int = 100, seed: int = 2025,
+                     output_csv_dir: str = "./uq_results_patient_laplace",
+                     output_plot_dir: str = "./uq_plots_patient/laplace_no_pool",
+                     raw_pred_path: Optional[str] = None, make_plots: bool = True) -> Optional[Dict]:
+    """Last-layer Laplace (``uq/laplace.py``): ``n_samples`` draws of the Dense head from the fitted ``state``,
+    then the raw dump, the detail CSV and the 24 metrics of the other two samplers; adds ``probit_accuracy``
+    (accuracy of the probit-corrected probability) and the state's scalars to the returned dict."""
+    print(f"\n===== Running Last-Layer Laplace Evaluation for: {model_eval_label} =====")
+    probs, mom = U.laplace_predict(model, state, X, n_samples=n_samples, seed=seed, return_moments=True)
+    if probs is None or probs.shape[0] != n_samples or probs.shape[1] != len(y):
+        print(f"Laplace prediction failed or returned unexpected shape for {model_eval_label}")
+        return None
+    if raw_pred_path is None:  # "" skips the dump
+        raw_pred_path = f"./laplace_raw_pred_{model_eval_label}.npy"
+    metrics = _finish(probs, y, patient_ids, model_eval_label, save_detailed_csv, output_csv_dir, output_plot_dir,
+                      n_bootstrap, seed, raw_pred_path, make_plots)
+    if metrics is not None:
+        metrics["probit_accuracy"] = float(((mom["probit_prob"] > 0.5).astype(int) == np.asarray(y).reshape(-1)).mean())
+        metrics.update(state.scalars())
+    return metrics
+
+
 def evaluate_mc_dropout_global(model, X_data_reshaped, y_data, model_eval_label: str, n_passes: int = 50,
                                n_bootstrap: int = 100, seed: int = 2025, bn_mode: str = "batch",
                                output_plot_dir: str = "./uq_plots/mc_dropout", make_plots: bool = True) -> Optional[Dict]:

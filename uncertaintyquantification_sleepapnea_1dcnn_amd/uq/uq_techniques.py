@@ -142,6 +142,10 @@ def deep_ensembles_predict(ensemble_models: List, x_test_data, as_numpy: bool = 
     return out
 
 
+# last-layer Laplace: the third sampler (one deterministic pass, draws of the Dense head; uq/laplace.py)
+from .laplace import fit_laplace, laplace_predict  # noqa: E402,F401
+
+
 # ===================== Uncertainty Metrics =====================
 def safe_entropy(probs: np.ndarray, axis: int = 1, epsilon: float = 1e-10) -> np.ndarray:
     """Entropy (nats) of probability rows after clipping to [eps, 1-eps] (SciPy renormalises)."""
