@@ -27,10 +27,12 @@
 | analyze_pass_convergence | (new) how many passes / members are enough: every metric against the count, with bands over random subsets, from one raw prediction dump |
 | analyze_laplace_patient_level | (new) last-layer Laplace UQ evaluation with per-window results: fits (or loads) the posterior of the Dense head, then the outputs of analyze_mcd_patient_level |
 | analyze_discrimination | (new) ROC / PR AUC and Mann-Whitney U (apnea vs normal, wrong vs right predictions) with window or patient-cluster bootstrap CIs, and the paired comparison of two detail CSVs |
+| analyze_recalibration | (new) temperature / Platt / beta recalibration of a raw prediction dump (fit set or patient cross-fit): calibration before and after on the same resamples, and the calibrated (T, N, 1) dump for the other analyze_* commands |
 """
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import sys
 
@@ -537,6 +539,81 @@ def analyze_discrimination(argv=None):
     if a.output_csv:
         os.makedirs(os.path.dirname(os.path.abspath(a.output_csv)), exist_ok=True)
         table.to_csv(a.output_csv, index=False)
+    return table
+
+
+def analyze_recalibration(argv=None):
+    ap = argparse.ArgumentParser(description="Temperature / Platt / beta recalibration of a raw prediction dump: fitted "
+                                             "on a fit set, or cross-fitted by patient, with ECE / MCE / Brier / NLL "
+                                             "before and after on the same bootstrap resamples; writes the calibrated "
+                                             "(T, N, 1) dump for the other analyze_* commands.")
+    ap.add_argument("--input_csv", type=str, default="./detailed_results_MCD.csv",
+                    help="per-window detail CSV, read for True_Label and Patient_ID")
+    ap.add_argument("--raw_pred", type=str, default="./mc_raw_pred0205.npy",
+                    help="(T, N[, 1]) .npy dump of the passes / members")
+    ap.add_argument("--fit_csv", type=str, default=None, help="detail CSV of a separate fit set (optional)")
+    ap.add_argument("--fit_raw_pred", type=str, default=None, help="raw dump of the fit set (optional)")
+    ap.add_argument("--method", choices=["temperature", "platt", "beta"], default="temperature")
+    ap.add_argument("--objective", choices=["joint", "member"], default="joint")
+    ap.add_argument("--folds", type=int, default=5, help="patient folds of the cross-fit (without a fit set)")
+    ap.add_argument("--n_bins", type=int, default=15)
+    ap.add_argument("--n_bootstrap", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--no_parity", action="store_true", help="draw with the device counter hash")
+    ap.add_argument("--output_raw_pred", type=str, default="./recalibrated_raw_pred.npy")
+    ap.add_argument("--output_csv", type=str, default="./recalibration_metrics.csv")
+    ap.add_argument("--state", type=str, default=None, help=".npz the fitted map (or the per-fold maps) is saved to")
+    ap.add_argument("--output_plot_dir", type=str, default="./uq_plots/recalibration")
+    ap.add_argument("--no_plots", action="store_true")
+    a = ap.parse_args(argv)
+    import pandas as pd
+
+    from ..uq import recalibration as RC
+
+    def load(csv, raw):
+        df = pd.read_csv(csv)
+        pred = np.load(raw).astype(np.float32)
+        n = pred.shape[1] if pred.ndim >= 2 else pred.shape[0]
+        if n != len(df):
+            raise ValueError(f"{raw} holds {n} windows, {csv} {len(df)}")
+        return pred, df
+
+    if bool(a.fit_csv) != bool(a.fit_raw_pred):
+        raise ValueError("--fit_csv and --fit_raw_pred go together")
+    pred, df = load(a.input_csv, a.raw_pred)
+    fit_pred, fit_y = None, None
+    if a.fit_csv:
+        fit_pred, fit_df = load(a.fit_csv, a.fit_raw_pred)
+        fit_y = fit_df["True_Label"].to_numpy()
+    label = os.path.splitext(os.path.basename(a.input_csv))[0]
+    pids = df["Patient_ID"].to_numpy() if "Patient_ID" in df.columns else None
+    res, det = RC.evaluate_recalibration(pred, df["True_Label"].to_numpy(), label, fit_predictions=fit_pred, fit_y=fit_y,
+                                         patient_ids=pids, n_folds=a.folds, method=a.method, objective=a.objective,
+                                         n_bootstrap=a.n_bootstrap, random_state=a.seed, parity=not a.no_parity,
+                                         n_bins=a.n_bins, output_plot_dir=a.output_plot_dir, make_plots=not a.no_plots,
+                                         seed=a.seed, return_details=True)
+    cols = ["before", "after", "diff", "diff_mean", "diff_ci_lower", "diff_ci_upper", "share_improved"]
+    table = pd.DataFrame([{"metric": m, **{c: res.get(f"{m}_{c}", np.nan) for c in cols}} for m in RC.METRICS],
+                         columns=["metric"] + cols)
+    print(f"{a.method} / {a.objective}, " + ("fitted on the fit set" if a.fit_csv else f"cross-fitted in {a.folds} folds"))
+    print({k: v for k, v in res.items() if k.startswith(("theta", "temperature", "fit_nll", "converged", "n_iter"))})
+    print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
+    for path in (a.output_csv, a.output_raw_pred, a.state):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    if a.output_csv:
+        table.to_csv(a.output_csv, index=False)
+    if a.output_raw_pred:
+        np.save(a.output_raw_pred, np.asarray(det["calibrated"], np.float32))
+        print(f"Saved the calibrated predictions to: {a.output_raw_pred}")
+    if a.state:
+        if a.fit_csv:
+            det["fit"].save(a.state)
+        else:
+            info = det["fit"]
+            np.savez(a.state, theta=info["theta"], fold=info["fold"],
+                     meta=np.array(json.dumps({"method": a.method, "objective": a.objective, "seed": a.seed,
+                                               "converged": info["converged"], "n_iter": info["n_iter"]})))
     return table
 
 

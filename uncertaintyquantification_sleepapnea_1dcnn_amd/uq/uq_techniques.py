@@ -144,6 +144,9 @@ def deep_ensembles_predict(ensemble_models: List, x_test_data, as_numpy: bool = 
 
 # last-layer Laplace: the third sampler (one deterministic pass, draws of the Dense head; uq/laplace.py)
 from .laplace import fit_laplace, laplace_predict  # noqa: E402,F401
+# post-hoc recalibration of any sampler's (T, N, 1) set: temperature / Platt / beta maps (uq/recalibration.py)
+from .recalibration import (Recalibrator, assign_folds, cross_recalibrate, evaluate_recalibration,  # noqa: E402,F401
+                            fit_recalibration)
 
 
 # ===================== Uncertainty Metrics =====================
