@@ -2,7 +2,10 @@
 + the kTrain / kLinear modes of ``csrc/generic_conv.hip``) for non-reference architectures -- pooled
 blocks, the 30 s single-channel window, odd filter counts and kernel size 1 -- against fp32 autograd
 over the reference ops with the same dropout masks; plus data-parallel (SyncBN) steps on 2 ranks
-sharing the GPU against the single-process step, for this path and the reference architecture's."""
+sharing the GPU against the single-process step, for this path and the reference architecture's.
+
+These are whole-step bounds (a few percent on a gradient).  The tight ones -- every kernel of this path on its
+own against float64, per entry -- are in ``test_generic_train_kernels_gpu.py``."""
 import numpy as np
 import pytest
 import torch

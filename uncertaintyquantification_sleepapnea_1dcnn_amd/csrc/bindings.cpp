@@ -74,7 +74,7 @@ hipError_t launch_generic_conv(const void* x, const void* wfrag, const float* ep
                                int n_win, unsigned pass_offset, unsigned window_offset, unsigned long long seed,
                                hipStream_t stream, int mode, int in_rs, int in_off, float* stats, long long x_rows,
                                int det_slots);
-hipError_t launch_gt_bn_finalize(const float* st, int nslots, int C, float inv_count, const float* gamma,
+hipError_t launch_gt_bn_finalize(const float* st, int nslots, int C, double inv_count, const float* gamma,
                                  const float* beta, float eps, float momentum, float* mmean, float* mvar, int update,
                                  float* bn, hipStream_t stream);
 hipError_t launch_gt_apply(const void* z, const float* bn, void* out, int n, int L, int C, int pool, int out_rs,
@@ -85,7 +85,7 @@ hipError_t launch_gt_bwd(int dz_mode, const void* z, const float* bn, const void
                          float inv_keep, unsigned skey, unsigned window_offset, float* bst, const float* coef,
                          const float* gamma, void* dz, int dz_rs, int dz_off, float* gbias, hipStream_t stream,
                          const unsigned* skey_dev, int det_slots, int f32);
-hipError_t launch_gt_bwd_finalize(const float* bst, int nslots, int C, float inv_count, float* coef, float* ggamma,
+hipError_t launch_gt_bwd_finalize(const float* bst, int nslots, int C, double inv_count, float* coef, float* ggamma,
                                   float* gbeta, const float* dbs, int bslots, int BC, float* gbias,
                                   hipStream_t stream);
 hipError_t launch_metrics_update(const float* p, const float* y, long long n, const float* thr, int n_thr,
@@ -935,7 +935,7 @@ void gt_bn_finalize(const at::Tensor& st, int64_t C, double inv_count, const at:
   const at::DeviceGuard guard(bn.device());
   // every slot of the table is summed (in a fixed order): kGtSlots atomic copies or the deterministic slots
   // (large tables in 64-slot ranges whose sums overwrite the ranges' first slots: st is consumed)
-  check(apneauq::launch_gt_bn_finalize(st.data_ptr<float>(), (int)(st.numel() / (2 * C)), (int)C, (float)inv_count,
+  check(apneauq::launch_gt_bn_finalize(st.data_ptr<float>(), (int)(st.numel() / (2 * C)), (int)C, inv_count,
                                        gamma.data_ptr<float>(),
                                        beta.data_ptr<float>(), (float)eps, (float)momentum, mmean.data_ptr<float>(),
                                        mvar.data_ptr<float>(), update ? 1 : 0, bn.data_ptr<float>(), cur_stream()),
@@ -1052,7 +1052,7 @@ void gt_bwd_finalize(const at::Tensor& bst, int64_t C, double inv_count, at::Ten
   }
   const at::DeviceGuard guard(C > 0 ? coef.device() : gbias->device());
   check(apneauq::launch_gt_bwd_finalize(C > 0 ? bst.data_ptr<float>() : nullptr, C > 0 ? (int)(bst.numel() / (2 * C)) : 0,
-                                        (int)C, (float)inv_count, C > 0 ? coef.data_ptr<float>() : nullptr,
+                                        (int)C, inv_count, C > 0 ? coef.data_ptr<float>() : nullptr,
                                         C > 0 ? ggamma.data_ptr<float>() : nullptr,
                                         C > 0 ? gbeta.data_ptr<float>() : nullptr, dbp, bslots, BC, gbp, cur_stream()),
         "gt_bwd_finalize");

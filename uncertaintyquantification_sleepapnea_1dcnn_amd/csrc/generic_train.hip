@@ -106,7 +106,7 @@ __device__ __forceinline__ double packed_sum(const float* st, int C, int range, 
   return __longlong_as_double((long long)(((unsigned long long)w[word + C] << 32) | w[word]));
 }
 
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* st, int nslots, int C, float inv_count,
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* st, int nslots, int C, double inv_count,
                                                           const float* gamma, const float* beta, float eps,
                                                           float momentum, float* mmean, float* mvar, int update,
                                                           float* bn, int packed) {
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void bwd_kernel(BwdArgs<T> A) {
 // Blocks [0, ceil(C / 16)) finalize the BN backward of one block; blocks after that (side job, no
 // node of its own) add the bias-gradient slot table (bslots, BC) of the block above it in fixed order:
 // lane j sums slots j, j + 16, ... (fp64), then the 16 lane sums in order -> reproducible.
-__global__ __launch_bounds__(256) void bwd_finalize_kernel(const float* bst, int nslots, int C, float inv_count,
+__global__ __launch_bounds__(256) void bwd_finalize_kernel(const float* bst, int nslots, int C, double inv_count,
                                                            float* coef, float* ggamma, float* gbeta, const float* dbs,
                                                            int bslots, int BC, float* gbias) {
   __shared__ double red[2][256];
@@ -395,7 +395,7 @@ inline int elem_grid(long long items, int per_block) {
 
 }  // namespace gtrain
 
-hipError_t launch_gt_bn_finalize(const float* st, int nslots, int C, float inv_count, const float* gamma,
+hipError_t launch_gt_bn_finalize(const float* st, int nslots, int C, double inv_count, const float* gamma,
                                  const float* beta, float eps, float momentum, float* mmean, float* mvar, int update,
                                  float* bn, hipStream_t stream) {
   if (nslots >= 4 * gtrain::kRange) {
@@ -503,7 +503,7 @@ hipError_t launch_gt_bwd(int dz_mode, const void* z, const float* bn, const void
                                 window_offset, bst, coef, gamma, dz, dz_rs, dz_off, gbias, stream, skey_dev, det_slots);
 }
 
-hipError_t launch_gt_bwd_finalize(const float* bst, int nslots, int C, float inv_count, float* coef, float* ggamma,
+hipError_t launch_gt_bwd_finalize(const float* bst, int nslots, int C, double inv_count, float* coef, float* ggamma,
                                   float* gbeta, const float* dbs, int bslots, int BC, float* gbias,
                                   hipStream_t stream) {
   if (gbias == nullptr) BC = 0;

@@ -279,10 +279,16 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs<T> A) {
   }
   const float z = wave_sum(part) + A.b[0];
   float dl = 0.f;
+  // e = exp(-|z|) in (0, 1] (expf: __expf rounds z log2(e) first, a relative error of ~|z| 2^-24 in the
+  // result).  q = e / (1 + e) is the sigmoid's small side at full relative accuracy; the other side is
+  // 1 - q.  p - y is formed from the side that does not cancel: a saturated p = 1.0f minus y = 1 is 0,
+  // where the gradient is -q.
+  const float e = expf(-fabsf(z));
   if (s < A.n) {
     const float yv = A.y[s];
-    const float p = 1.0f / (1.0f + __expf(-z));
-    dl = (p - yv) * A.inv_gb;
+    const float q = e / (1.0f + e);
+    const float p = z >= 0.f ? 1.0f / (1.0f + e) : q;
+    dl = (z >= 0.f ? (1.0f - yv) - q : q - yv) * A.inv_gb;
     if (lane == 0) {
       A.prob[s] = p;
       A.dlog[s] = dl;
@@ -294,7 +300,7 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs<T> A) {
   float* wloss = dls + 4;
   if (lane == 0) {
     dls[wave] = dl;
-    wloss[wave] = s < A.n ? fmaxf(z, 0.f) - z * A.y[s] + log1pf(__expf(-fabsf(z))) : 0.f;
+    wloss[wave] = s < A.n ? fmaxf(z, 0.f) - z * A.y[s] + log1pf(e) : 0.f;
   }
   __syncthreads();
   float* rec = A.part != nullptr ? A.part + (long long)blockIdx.x * (A.C + 2) : nullptr;

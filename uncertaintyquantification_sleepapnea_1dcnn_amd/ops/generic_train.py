@@ -109,8 +109,13 @@ class GenericTrainWorkspace:
         self.xin = [torch.zeros(2 * self.pads[l] + B * self.rs[l], self.ch[l], dtype=bf, device=dev) for l in range(nl)]
         self.z = [torch.empty(B * self.L[l], self.ch[l + 1], dtype=bf, device=dev) for l in range(nl)]
         self.hlast = torch.empty(B * self.L[-1], self.ch[-1], dtype=bf, device=dev)
-        # forward moment slots: (slots, 2, C); deterministic: one per (conv workgroup of 128 rows, wave row)
-        fslots = [max(SLOTS, 2 * -(-B * self.L[l] // 128)) if self.det else SLOTS for l in range(nl)]
+        # forward moment slots: (slots, 2, C), one per (conv workgroup of 128 rows, wave row), written with
+        # plain stores and added in a fixed order -- in atomic mode too.  fp32 atomics into 16 shared slots
+        # left the last bit of mean / var to the order of the adds; one bf16 store of the next layer's input
+        # that such a bit tips over its rounding boundary (a few of the ~10^5 of a batch sit that close)
+        # moved the loss of the SAME step by 4e-4 from run to run.  The forward of a step is now
+        # reproducible in either mode; atomic mode keeps its atomics in the backward sums, wgrad and head.
+        fslots = [max(SLOTS, 2 * -(-B * self.L[l] // 128)) for l in range(nl)]
         sizes = [fslots[l] * 2 * self.ch[l + 1] for l in range(nl)]
         # + the fp16x3 operand maxima (fp32 bits as int32, atomicMax): [conv input of block l] * nl,
         # [dZ of block l] * nl -- zeroed with the moment slots every forward
@@ -250,7 +255,7 @@ def _forward(ws: GenericTrainWorkspace, n: int, global_n: int, seed: int, pass_i
         else:
             conv = o.gf_conv if ws.f32 else o.gt_conv
             conv(ws.xin[l], wf[l], v[f"conv1d_{i}/bias"], ws.z[l], ws.st[l], n, L, cin, cout, ws.ks[l], 1,
-                 ws.rs[l], 2 * ws.pads[l], ws.det)
+                 ws.rs[l], 2 * ws.pads[l], True)  # per-workgroup moment slots in either mode (see fslots)
         if sync is not None:
             sync(ws.st[l])
         # consumes ws.st[l]: a large slot table (deterministic mode) is summed in place, its first slots
