@@ -8,6 +8,7 @@
 // step_dev the bias correction is computed on the device from the iteration counter, so a captured
 // HIP graph of the training step replays correctly (ops/train_ops.py:GraphedTrainStep).
 #include "common.h"
+#include "misc_api.h"
 
 namespace apneauq {
 

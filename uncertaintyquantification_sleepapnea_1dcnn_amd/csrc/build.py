@@ -1,7 +1,8 @@
 """In-tree build of the apneauq HIP extension for gfx950 (MI355X).
 
 Every ``*.hip`` file under ``csrc/`` is compiled by ``hipcc --offload-arch=gfx950`` and the
-torch.library bindings (``bindings.cpp``) by the host C++ compiler; the result is linked into
+torch.library bindings (``bindings.cpp`` and one ``*_bindings.cpp`` per kernel family: fused, uq, recal,
+train, generic, x3) by the host C++ compiler, against the shared ``*_api.h`` / ``bind_util.h`` headers; the result is linked into
 ``<package>/_apneauq_hip.so`` and loaded with ``torch.ops.load_library``.  No hipify step, no
 JIT cache: the ``.so`` sits in the source tree so it travels with the repository snapshot.
 

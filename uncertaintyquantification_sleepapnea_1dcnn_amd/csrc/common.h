@@ -55,6 +55,17 @@ __host__ __device__ __forceinline__ uint32_t sample_key(uint32_t skey, uint32_t 
   return mix32(skey ^ mix32(sample + 0x2545F491u));
 }
 
+// Bootstrap resampling draw (uq_reduce / uq_calib / uq_patient / uq_rank; ops/rng.py boot_draw is the same
+// function on tensors): draw j of replicate b over n items.  One definition: the same seed gives the same
+// resamples in every kernel and on every shard.
+__device__ __forceinline__ unsigned boot_key(unsigned seed, unsigned b) {
+  return mix32(seed ^ mix32(b * 0x9E3779B9u + 0x7F4A7C15u));
+}
+__device__ __forceinline__ unsigned boot_draw(unsigned bkey, unsigned j, int n) {
+  const unsigned hsh = mix32(bkey ^ mix32(j));
+  return (unsigned)(((unsigned long long)hsh * (unsigned long long)n) >> 32);
+}
+
 // 16-bit uniforms of channels (c, c+1), c even, at time step t.
 __device__ __forceinline__ uint32_t dropout_bits2(uint32_t skey, uint32_t t, uint32_t c_even) {
   return mix32(skey ^ ((t << 9) | (c_even >> 1)));

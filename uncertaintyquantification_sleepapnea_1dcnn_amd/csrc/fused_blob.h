@@ -2,13 +2,13 @@
 // no-pool CNN; fused_pooled.hip: the same CNN with MaxPool1D(2) after blocks 1-5).  Both read one
 // model's packed parameters (ops/fused.py:pack_blob) from the same byte offsets.
 #pragma once
+#include "arch_tables.h"
 
 namespace apneauq {
 namespace fused {
 
-// channel / kernel-size table of the default spec (cnn_baseline_train.py:59-86)
-constexpr int C[7] = {4, 128, 192, 224, 96, 256, 96};
-constexpr int KS[6] = {7, 5, 3, 7, 9, 9};
+using arch::C;
+using arch::KS;
 
 __host__ __device__ constexpr int ksteps(int l) { return (C[l] * KS[l] + 31) / 32; }
 __host__ __device__ constexpr int wbytes(int l) { return ksteps(l) * (C[l + 1] / 16) * 1024; }

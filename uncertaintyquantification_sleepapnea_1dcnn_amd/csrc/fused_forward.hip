@@ -21,6 +21,7 @@
 //   LDS per workgroup ~75 KiB -> 2 workgroups (8 waves) per CU.
 #include "common.h"
 #include "fused_blob.h"
+#include "fused_api.h"
 
 namespace apneauq {
 namespace fused {

@@ -34,6 +34,7 @@
 //   LDS per workgroup ~78 KiB -> 2 workgroups (8 waves) per CU.  Measured: profiles/pooled_fused_r3.md.
 #include "common.h"
 #include "fused_blob.h"
+#include "fused_api.h"
 
 namespace apneauq {
 namespace tiled {

@@ -29,6 +29,7 @@
 // 16-row tile) read finite LDS bytes and are never stored.
 #include "common.h"
 #include "fused_blob.h"
+#include "fused_api.h"
 
 namespace apneauq {
 namespace tiled3 {

@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "generic_api.h"
 
 #include <type_traits>
 

@@ -19,6 +19,7 @@
 // Channel-group mapping of the elementwise kernels: a thread owns 4 consecutive channels of one
 // row (8-byte bf16x4 accesses), G = C/4 <= 256 groups across the block, 256 / G rows per sweep.
 #include "common.h"
+#include "generic_api.h"
 
 namespace apneauq {
 namespace gtrain {

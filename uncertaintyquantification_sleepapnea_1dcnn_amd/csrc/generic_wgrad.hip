@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "generic_api.h"
 
 namespace apneauq {
 namespace gwgrad {

@@ -18,10 +18,9 @@
 //                      row group writes its own partial (plain stores), summed in a fixed order by the
 //                      ordered reduce of generic_wgrad.hip: deterministic weight gradients.
 #include "common.h"
+#include "generic_api.h"
 
 namespace apneauq {
-
-hipError_t launch_ordered_sum(const float* part, int nrows, long long ncols, float* out, hipStream_t st);
 
 namespace gf32 {
 

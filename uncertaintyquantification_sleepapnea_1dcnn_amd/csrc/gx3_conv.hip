@@ -34,10 +34,9 @@
 //     transposing ds_read_b64_tr_b16), every tap's accumulators in registers; row-group partials
 //     summed in a fixed order (deterministic).
 #include "common.h"
+#include "generic_api.h"
 
 namespace apneauq {
-
-hipError_t launch_ordered_sum(const float* part, int nrows, long long ncols, float* out, hipStream_t st);
 
 namespace gx3 {
 

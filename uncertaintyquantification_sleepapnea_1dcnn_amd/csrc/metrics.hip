@@ -14,6 +14,7 @@
 // lands in the last bucket (and counts as "not > 0.5" for the accuracy); per-block LDS histograms are flushed with one 64-bit
 // atomic per non-empty bin.
 #include "common.h"
+#include "misc_api.h"
 
 namespace apneauq {
 namespace metrics {

@@ -11,6 +11,7 @@
 // host or here, so distances are the exact sum of squared differences in a fixed feature order (no
 // ||a||^2 + ||b||^2 - 2ab cancellation) and the neighbour order is (distance, index) lexicographic.
 #include "common.h"
+#include "misc_api.h"
 
 namespace apneauq {
 namespace prep {

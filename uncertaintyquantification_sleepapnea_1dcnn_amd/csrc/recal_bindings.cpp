@@ -1,30 +1,9 @@
 // torch.library registration of the recalibration kernels (uq_recal.hip), namespace torch.ops.apneauq.
-#include <ATen/ATen.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/library.h>
-
-#include <hip/hip_runtime_api.h>
-
-#include <cstdint>
-
-namespace apneauq {
-int recal_max_t();
-int recal_max_q();
-int recal_max_f();
-int recal_max_lds();
-long long recal_lds_bytes(int T, int F, int Q);
-hipError_t launch_recal_sums(const float* probs, const unsigned char* y, const int* fold, const double* thetas,
-                             long long n, int T, int Q, int F, int objective, long long range_len, int grid,
-                             double* part, double* out, hipStream_t stream);
-hipError_t launch_recal_apply(const float* probs, const int* fold, const double* thetas, long long n, int T, int F,
-                              float* out, hipStream_t stream);
-}  // namespace apneauq
+#include "bind_util.h"
+#include "uq_api.h"
 
 namespace {
-
-inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
-inline void check(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, " failed: ", hipGetErrorString(e)); }
+using namespace apneauq::bind;
 
 void check_fold(const at::Tensor& fold, int64_t n, int64_t F, const char* what) {
   TORCH_CHECK(fold.is_cuda() && fold.scalar_type() == at::kInt && fold.dim() == 1 &&

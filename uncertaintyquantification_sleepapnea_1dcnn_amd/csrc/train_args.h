@@ -4,7 +4,9 @@
 #pragma once
 #include <type_traits>
 
+#include "arch_tables.h"
 #include "common.h"
+#include "train_ctx.h"
 
 namespace apneauq {
 namespace train {
@@ -14,78 +16,14 @@ typedef short v4i16 __attribute__((ext_vector_type(4)));
 constexpr int kL = 60, kSR = 64, kSlots = 2, kR = 128, kRT = 8, kHalo = 4, kRows = 136;
 constexpr int kRS = 256 * 2 + 32;  // LDS row stride (bytes) of the staged activation tiles
 constexpr int kThreads = 256;
-constexpr int C[7] = {4, 128, 192, 224, 96, 256, 96};
+constexpr int C[7] = {4, 128, 192, 224, 96, 256, 96};  // the kernels' own objects; == arch::C / arch::KS:
 constexpr int KS[6] = {7, 5, 3, 7, 9, 9};
-
-struct Layer {
-  const gbf16x8* wf;   // forward fragments  (ksteps, Cout/16, 64, 8)
-  const gbf16x8* wd;   // dgrad fragments    (ksteps', Cin/16, 64, 8)
-  const float* bias;
-  const float* gamma;
-  const float* beta;
-  float* mmean;
-  float* mvar;
-  float* gw;           // dW (k, Cin, Cout) fp32, in the flat gradient buffer
-  float* gb;
-  float* ggamma;
-  float* gbeta;
-  __bf16* R;           // PL (rows, C) post-ReLU, pre-BN
-  __bf16* dY;          // PL (rows, C) gradient wrt BN output (blocks 1..5)
-  __bf16* dZ;          // PL (rows, C) gradient wrt the conv pre-activation, written by dgrad_l (l >= 1)
-  double* st;          // [slots][groups][2][C] forward moment sums (sum r, sum r^2), fp64
-  double* bst;         // [slots][2][C] backward sums (sum dY, sum dY * xhat), fp64: partial sums of
-                       // data-parallel ranks then add exactly (a 2-rank step computes the 1-rank
-                       // BN-backward coefficients bit for bit in deterministic mode)
-  unsigned thr;        // dropout threshold (16-bit units) and 1/(1-p)
-  float dsc;
-};
-
-struct Args {
-  Layer L[6];
-  const __bf16* x;     // PL (rows, 4)
-  const float* y;      // labels (B)
-  const float* dense_w;
-  const float* dense_b;
-  float* g_dense_w;
-  float* g_dense_b;
-  float* logits;       // (B)
-  float* dlogit;       // (B)
-  float* loss_sum;     // (1)
-  int B;               // samples in this launch (T*N for batch-BN MC Dropout)
-  int n_win;           // samples per stats group (B for training, N for MC Dropout)
-  int groups;          // number of stats groups
-  unsigned pass_base;  // dropout pass id of group 0
-  unsigned window_offset;
-  unsigned long long seed;
-  int dropout;
-  float inv_count;     // 1 / (samples per group * 60) — BN moment normaliser
-  float inv_batch;     // 1 / global batch size — BCE mean
-  float eps;
-  float momentum;
-  const unsigned* pass_dev;  // optional device step counter added to pass_base (HIP-graph replays)
-  int st_groups;       // groups the moment buffers are allocated for (>= groups)
-  float* wpart;        // wgrad partials [row group][K*Cin*Cout + Cout] (nullptr: fp32 atomics)
-  float* det;          // deterministic mode (training, one stats group): per-workgroup / per-sample
-                       // partial sums of the BN moments, head and dgrad statistics go here with
-                       // plain stores and det_reduce_kernel adds them in a fixed order (nullptr:
-                       // atomics, whose summation order varies run to run)
-  int shared0;         // batch-BN MC Dropout: block 1 (no dropout before it) is computed once for the
-                       // n_win windows (stats group 0, R_0 unencoded, indexed by window) and shared by
-                       // every pass; block 2's staging applies block 1's dropout from the hash
-  float* tab;          // single-device training: per-layer BN parameter table [6][kTabRows][256] fp32
-                       // (mean, rstd, gamma*rstd, beta - mean*gamma*rstd, mean dY, mean dY*xhat), written
-                       // once per step by tab_kernel; the ~512 workgroups of each backward kernel read a
-                       // few KB instead of each re-summing 16 fp64 slots per channel from the device-
-                       // coherent moment buffers (~100 MB per dgrad launch).  nullptr: slot sums
-  float* hpart;        // training head: per-workgroup dense-weight / loss / dense-bias sums go to
-                       // [kStatSlots][96 + 2] fp32 slots (workgroup % kStatSlots) that bn_finalize adds
-                       // in slot order, instead of 256 workgroups' atomics on the same 98 addresses
-                       // (nullptr: direct atomics)
-  int bwd_self;        // dgrad / wgrad launch flag (not in the ctx): sum the backward BN rows of block l
-                       // from bst[l] themselves instead of reading the table rows that wgrad_reduce's
-                       // side job writes -- so a wgrad chain on a second stream (GraphedTrainStep
-                       // overlap) carries no dependency back into the dgrad chain
-};
+constexpr bool tables_match() {
+  for (int i = 0; i < 7; ++i)
+    if (C[i] != arch::C[i] || (i < 6 && KS[i] != arch::KS[i])) return false;
+  return true;
+}
+static_assert(tables_match(), "train::C / train::KS differ from arch_tables.h");
 
 template <typename T>
 __device__ __forceinline__ T gld(const void* p) {

@@ -32,6 +32,8 @@
 #include <cstdlib>
 
 #include "train_args.h"
+#include "misc_api.h"
+#include "train_api.h"
 
 namespace apneauq {
 namespace train {
@@ -1625,10 +1627,6 @@ constexpr bool wg_lds_fits() {
 static_assert(wg_lds_fits<0>() && wg_lds_fits<1>() && wg_lds_fits<2>() && wg_lds_fits<3>() && wg_lds_fits<4>() &&
                   wg_lds_fits<5>(),
               "wgrad tiles must fit two 4-wave (or one 8-wave) workgroups per CU");
-
-int train_args_size() { return (int)sizeof(Args); }
-
-int train_layer_size() { return (int)sizeof(train::Layer); }
 
 __global__ void bump_counters_kernel(int* c, int n) {
   if (threadIdx.x < n) c[threadIdx.x] += 1;

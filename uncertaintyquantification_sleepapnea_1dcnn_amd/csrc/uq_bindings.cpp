@@ -1,0 +1,349 @@
+// torch.library registration of the UQ reduction kernels (uq_reduce.hip, uq_calib.hip, uq_patient.hip, uq_rank.hip,
+// uq_laplace.hip, uq_converge.hip), namespace torch.ops.apneauq.
+#include "bind_util.h"
+#include "uq_api.h"
+
+#include <tuple>
+
+namespace {
+using namespace apneauq::bind;
+
+at::Tensor uq_reduce(const at::Tensor& probs) {
+  TORCH_CHECK(probs.is_cuda() && probs.scalar_type() == at::kFloat && probs.dim() == 2,
+              "uq_reduce: probs must be a (T, N) float32 GPU tensor");
+  auto p = probs.contiguous();
+  const at::DeviceGuard guard(p.device());
+  auto out = at::empty({7, p.size(1)}, p.options());
+  check(apneauq::launch_uq_reduce(p.data_ptr<float>(), (int)p.size(0), (int)p.size(1), out.data_ptr<float>(),
+                                  cur_stream()),
+        "uq_reduce");
+  return out;
+}
+
+at::Tensor bootstrap(const at::Tensor& metrics, const at::Tensor& y, const c10::optional<at::Tensor>& idx,
+                     int64_t seed, int64_t n_boot) {
+  TORCH_CHECK(metrics.is_cuda() && metrics.scalar_type() == at::kFloat && metrics.dim() == 2 && metrics.size(0) == 7,
+              "bootstrap: metrics must be the (7, N) output of uq_reduce");
+  const int64_t n = metrics.size(1);
+  auto m = metrics.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.numel() == n, "bootstrap: y must be (N,) on the GPU");
+  at::Tensor ii;
+  const int* ip = opt_idx(idx, n_boot, n, "bootstrap: idx must be (B, N)", ii);
+  const at::DeviceGuard guard(m.device());
+  auto out = at::empty({n_boot, 6}, m.options().dtype(at::kDouble));
+  check(apneauq::launch_bootstrap(m.data_ptr<float>(), yy.data_ptr<int>(), ip, (unsigned)seed, (int)n, (int)n_boot,
+                                  out.data_ptr<double>(), cur_stream()),
+        "bootstrap");
+  return out;
+}
+
+// Sharded bootstrap: raw (B, 8) sums over the draws landing in this rank's windows
+// [lo, lo + n_loc) of n_global; summed over ranks by the caller, then turned into the 6 means.
+at::Tensor bootstrap_partial(const at::Tensor& metrics, const at::Tensor& y, const c10::optional<at::Tensor>& idx,
+                             int64_t seed, int64_t n_boot, int64_t n_global, int64_t lo) {
+  TORCH_CHECK(metrics.is_cuda() && metrics.scalar_type() == at::kFloat && metrics.dim() == 2 && metrics.size(0) == 7,
+              "bootstrap_partial: metrics must be the (7, n_loc) output of uq_reduce");
+  const int64_t n_loc = metrics.size(1);
+  TORCH_CHECK(lo >= 0 && lo + n_loc <= n_global && n_global < (int64_t(1) << 31), "bootstrap_partial: bad shard");
+  auto m = metrics.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.numel() == n_loc, "bootstrap_partial: y must be (n_loc,) on the GPU");
+  at::Tensor ii;
+  const int* ip = opt_idx(idx, n_boot, n_global, "bootstrap_partial: idx must be (B, n_global)", ii);
+  const at::DeviceGuard guard(m.device());
+  auto out = at::empty({n_boot, 8}, m.options().dtype(at::kDouble));
+  check(apneauq::launch_bootstrap_partial(m.data_ptr<float>(), yy.data_ptr<int>(), ip, (unsigned)seed, (int)n_global,
+                                          (int)lo, (int)n_loc, (int)n_boot, out.data_ptr<double>(), cur_stream()),
+        "bootstrap_partial");
+  return out;
+}
+
+// Calibration / selective prediction (uq_calib.hip): per-window integer records, then the bootstrap
+// histogram sums.  Limits: K <= 32 bins, J <= 64 thresholds, n <= 2^27 (sum nll_q stays below 2^63).
+at::Tensor calib_prep(const at::Tensor& p, const at::Tensor& score, const at::Tensor& y, const at::Tensor& thr,
+                      int64_t n_bins) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.dim() == 1, "calib_prep: p must be (N,) float32 on the GPU");
+  const int64_t n = p.size(0), n_thr = thr.numel();
+  TORCH_CHECK(score.is_cuda() && score.scalar_type() == at::kFloat && score.dim() == 1 && score.size(0) == n,
+              "calib_prep: score must be (N,) float32 on the GPU");
+  TORCH_CHECK(thr.is_cuda() && thr.scalar_type() == at::kFloat && thr.dim() == 1,
+              "calib_prep: thr must be (J,) float32 on the GPU");
+  TORCH_CHECK(n_bins >= 1 && n_bins <= 32, "calib_prep: n_bins must be in 1..32");
+  TORCH_CHECK(n_thr <= 64, "calib_prep: at most 64 thresholds");
+  TORCH_CHECK(n <= (int64_t(1) << 27), "calib_prep: at most 2^27 windows");
+  auto pp = p.contiguous(), ss = score.contiguous(), tt = thr.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.dim() == 1 && yy.size(0) == n, "calib_prep: y must be (N,) on the GPU");
+  const at::DeviceGuard guard(pp.device());
+  auto rec = at::empty({n, 4}, pp.options().dtype(at::kInt));
+  check(apneauq::launch_calib_prep(pp.data_ptr<float>(), ss.data_ptr<float>(), yy.data_ptr<int>(), tt.data_ptr<float>(),
+                                   (int)n, (int)n_bins, (int)n_thr, rec.data_ptr<int>(), cur_stream()),
+        "calib_prep");
+  return rec;
+}
+
+at::Tensor calib_bootstrap(const at::Tensor& rec, const c10::optional<at::Tensor>& idx, int64_t seed, int64_t n_boot,
+                           int64_t n_global, int64_t lo, int64_t n_bins, int64_t n_thr, int64_t slices) {
+  TORCH_CHECK(rec.is_cuda() && rec.scalar_type() == at::kInt && rec.dim() == 2 && rec.size(1) == 4,
+              "calib_bootstrap: rec must be the (n_loc, 4) int32 output of calib_prep");
+  const int64_t n_loc = rec.size(0);
+  TORCH_CHECK(n_bins >= 1 && n_bins <= 32, "calib_bootstrap: n_bins must be in 1..32");
+  TORCH_CHECK(n_thr >= 0 && n_thr <= 64, "calib_bootstrap: n_thr must be in 0..64");
+  TORCH_CHECK(n_global >= 1 && n_global <= (int64_t(1) << 27), "calib_bootstrap: n_global must be in 1..2^27");
+  TORCH_CHECK(lo >= 0 && lo + n_loc <= n_global, "calib_bootstrap: bad shard");
+  TORCH_CHECK(n_boot >= 0 && n_boot < (int64_t(1) << 31), "calib_bootstrap: bad n_boot");
+  TORCH_CHECK(slices >= 1 && slices <= 1024, "calib_bootstrap: slices must be in 1..1024");
+  auto rr = rec.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rr.data_ptr()) % 16 == 0, "calib_bootstrap: 16-B alignment required");
+  at::Tensor ii;
+  const int* ip = opt_idx(idx, n_boot, n_global, "calib_bootstrap: idx must be (B, n_global)", ii);
+  const int64_t n_col = 3 * n_bins + 4 * (n_thr + 1) + 2;
+  const at::DeviceGuard guard(rr.device());
+  auto slabs = at::empty({n_boot, slices, n_col}, rr.options().dtype(at::kLong));
+  check(apneauq::launch_calib_bootstrap(rr.data_ptr<int>(), ip, (unsigned)seed, (int)n_global, (int)lo, (int)n_loc,
+                                        (int)n_boot, (int)n_bins, (int)n_thr, (int)slices,
+                                        reinterpret_cast<long long*>(slabs.data_ptr<int64_t>()), cur_stream()),
+        "calib_bootstrap");
+  return slices == 1 ? slabs.select(1, 0) : slabs.sum(1);
+}
+
+// Patient-level sums (uq_patient.hip).  Limits: n <= 2^27 windows (a fixed-point term is at most 2^32, so every
+// rec sum stays below 2^59), T <= 65536, P <= 2^24 and T P < 2^31.  Windows with a code outside [0, P) are skipped.
+std::tuple<at::Tensor, at::Tensor> patient_reduce(const at::Tensor& probs, const at::Tensor& m, const at::Tensor& y,
+                                                  const at::Tensor& code, int64_t n_pat) {
+  TORCH_CHECK(probs.is_cuda() && probs.scalar_type() == at::kFloat && probs.dim() == 2,
+              "patient_reduce: probs must be a (T, n) float32 GPU tensor");
+  const int64_t t_count = probs.size(0), n = probs.size(1);
+  TORCH_CHECK(m.is_cuda() && m.scalar_type() == at::kFloat && m.dim() == 2 && m.size(0) == 7 && m.size(1) == n,
+              "patient_reduce: m must be the (7, n) output of uq_reduce");
+  TORCH_CHECK(t_count >= 1 && t_count <= 65536, "patient_reduce: T must be in 1..65536");
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 27), "patient_reduce: n must be in 1..2^27");
+  TORCH_CHECK(n_pat >= 1 && n_pat <= (int64_t(1) << 24) && t_count * n_pat < (int64_t(1) << 31),
+              "patient_reduce: P must be in 1..2^24 with T P < 2^31");
+  TORCH_CHECK(code.is_cuda() && code.scalar_type() == at::kInt && code.dim() == 1 && code.size(0) == n,
+              "patient_reduce: code must be (n,) int32 on the GPU");
+  auto pp = probs.contiguous(), mm = m.contiguous(), cc = code.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.dim() == 1 && yy.size(0) == n, "patient_reduce: y must be (n,) on the GPU");
+  const at::DeviceGuard guard(pp.device());
+  auto pass_pos = at::zeros({t_count, n_pat}, pp.options().dtype(at::kInt));
+  auto rec = at::zeros({n_pat, 12}, pp.options().dtype(at::kLong));
+  check(apneauq::launch_patient_reduce(pp.data_ptr<float>(), mm.data_ptr<float>(), yy.data_ptr<int>(),
+                                       cc.data_ptr<int>(), (int)t_count, (int)n, (int)n_pat, pass_pos.data_ptr<int>(),
+                                       reinterpret_cast<long long*>(rec.data_ptr<int64_t>()), cur_stream()),
+        "patient_reduce");
+  return {pass_pos, rec};
+}
+
+// Patient-cluster bootstrap: (B, 41) sums of the (P, 25) per-patient records over P draws per replicate.
+// Limits: P <= 2^20 and P max|prec| < 2^63, so that no replicate (which may draw one patient P times) overflows.
+at::Tensor patient_bootstrap(const at::Tensor& prec, const c10::optional<at::Tensor>& idx, int64_t seed,
+                             int64_t n_boot) {
+  TORCH_CHECK(prec.is_cuda() && prec.scalar_type() == at::kLong && prec.dim() == 2 && prec.size(1) == 25,
+              "patient_bootstrap: prec must be a (P, 25) int64 GPU tensor");
+  const int64_t n_pat = prec.size(0);
+  TORCH_CHECK(n_pat >= 1 && n_pat <= (int64_t(1) << 20), "patient_bootstrap: P must be in 1..2^20");
+  TORCH_CHECK(n_boot >= 0 && n_boot < (int64_t(1) << 31), "patient_bootstrap: bad n_boot");
+  auto rr = prec.contiguous();
+  const int64_t lo = rr.min().item<int64_t>(), hi = rr.max().item<int64_t>();
+  const int64_t lim = INT64_MAX / n_pat;
+  TORCH_CHECK(lo >= -lim && hi <= lim, "patient_bootstrap: P max|prec| must stay below 2^63");
+  at::Tensor ii;
+  const int* ip = opt_idx(idx, n_boot, n_pat, "patient_bootstrap: idx must be (B, P)", ii);
+  const at::DeviceGuard guard(rr.device());
+  auto out = at::empty({n_boot, 41}, rr.options());
+  check(apneauq::launch_patient_bootstrap(reinterpret_cast<const long long*>(rr.data_ptr<int64_t>()), ip, (unsigned)seed,
+                                          (int)n_pat, (int)n_boot, reinterpret_cast<long long*>(out.data_ptr<int64_t>()),
+                                          cur_stream()),
+        "patient_bootstrap");
+  return out;
+}
+
+// Rank statistics (uq_rank.hip).  rank_count: (B, n_sorted) int32 multiplicities of the sorted windows in replicates
+// b0 .. b0 + B - 1, rows 16-B aligned (the result is a view of a (B, n_sorted rounded up to 4) buffer).  Limits:
+// at most 2^27 draws per replicate, so a replicate's total weight stays below 2^31.
+at::Tensor rank_count(const at::Tensor& pos, const c10::optional<at::Tensor>& idx, int64_t seed, int64_t b0,
+                      int64_t n_boot, int64_t n_sorted) {
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.dim() == 1,
+              "rank_count: pos must be (n,) int32 on the GPU");
+  const int64_t n_draw = pos.size(0);
+  TORCH_CHECK(n_draw >= 1 && n_draw <= (int64_t(1) << 27), "rank_count: n must be in 1..2^27");
+  TORCH_CHECK(n_sorted >= 1 && n_sorted <= n_draw, "rank_count: n_sorted must be in 1..n");
+  TORCH_CHECK(n_boot >= 0 && b0 >= 0 && b0 + n_boot < (int64_t(1) << 31), "rank_count: bad replicate range");
+  auto pp = pos.contiguous();
+  at::Tensor ii;
+  const int* ip = opt_idx(idx, n_boot, n_draw, "rank_count: idx must be (B, n)", ii);
+  const int64_t stride = (n_sorted + 3) / 4 * 4;
+  const at::DeviceGuard guard(pp.device());
+  auto w = at::zeros({n_boot, stride}, pp.options());
+  check(apneauq::launch_rank_count(pp.data_ptr<int>(), ip, (unsigned)seed, (int)n_draw, (int)n_sorted, (int)b0,
+                                   (int)n_boot, (long long)stride, w.data_ptr<int>(), cur_stream()),
+        "rank_count");
+  return w.narrow(1, 0, n_sorted);
+}
+
+// rank_scan: (B, 6) int64 sums W, P, U2, groups, prauc_q, ap_q of weight rows over the sorted windows.  bounds
+// (G + 1,) are the split points (tie-group starts, ops/rank.py:split_bounds); the result does not depend on G.
+// Limits: n <= 2^27, G <= 64, weights non-negative with every row's total below 2^31 (checked on the totals).
+at::Tensor rank_scan(const at::Tensor& w, const at::Tensor& packed, const at::Tensor& bounds) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kInt && w.dim() == 2, "rank_scan: w must be (B, n) int32 on the GPU");
+  const int64_t n_boot = w.size(0), n = w.size(1);
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 27), "rank_scan: n must be in 1..2^27");
+  TORCH_CHECK(n_boot >= 0 && n_boot < (int64_t(1) << 31), "rank_scan: bad number of replicates");
+  TORCH_CHECK(packed.is_cuda() && packed.scalar_type() == at::kByte && packed.dim() == 1 && packed.size(0) == n,
+              "rank_scan: packed must be (n,) uint8 on the GPU");
+  TORCH_CHECK(bounds.is_cuda() && bounds.scalar_type() == at::kInt && bounds.dim() == 1 && bounds.size(0) >= 2 &&
+                  bounds.size(0) <= apneauq::rank_max_splits() + 1,
+              "rank_scan: bounds must be (G + 1,) int32 on the GPU, G in 1..64");
+  const int64_t splits = bounds.size(0) - 1;
+  const at::DeviceGuard guard(w.device());
+  // rows on 16-B boundaries for the vector loads: the view rank_count returns qualifies, anything else is copied
+  at::Tensor ww = w;
+  const int64_t stride = (n + 3) / 4 * 4;
+  if (n_boot > 0 && (w.stride(1) != 1 || w.stride(0) % 4 != 0 || w.stride(0) < n ||
+                     reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 != 0)) {
+    auto buf = at::zeros({n_boot, stride}, w.options());
+    buf.narrow(1, 0, n).copy_(w);
+    ww = buf.narrow(1, 0, n);
+  }
+  auto pk = packed.contiguous(), bb = bounds.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pk.data_ptr()) % 4 == 0, "rank_scan: 4-B alignment of packed required");
+  auto tot = at::empty({n_boot, splits, 3}, w.options().dtype(at::kLong));
+  auto part = at::empty({n_boot, splits, 4}, w.options().dtype(at::kLong));
+  auto out = at::empty({n_boot, 6}, w.options().dtype(at::kLong));
+  if (n_boot == 0) return out;
+  const long long row = n_boot > 1 ? ww.stride(0) : stride;
+  check(apneauq::launch_rank_totals(ww.data_ptr<int>(), row, pk.data_ptr<uint8_t>(), bb.data_ptr<int>(), (int)n,
+                                    (int)n_boot, (int)splits, reinterpret_cast<long long*>(tot.data_ptr<int64_t>()),
+                                    cur_stream()),
+        "rank_totals");
+  auto t = tot.sum(1);  // (B, 3): positives, negatives, negative weights
+  TORCH_CHECK(t.select(1, 2).max().item<int64_t>() == 0, "rank_scan: weights must be non-negative");
+  auto total = t.select(1, 0) + t.select(1, 1);
+  TORCH_CHECK(total.max().item<int64_t>() < (int64_t(1) << 31), "rank_scan: a replicate's total weight must stay below 2^31");
+  check(apneauq::launch_rank_scan(ww.data_ptr<int>(), row, pk.data_ptr<uint8_t>(), bb.data_ptr<int>(),
+                                  reinterpret_cast<const long long*>(tot.data_ptr<int64_t>()), (int)n, (int)n_boot,
+                                  (int)splits, reinterpret_cast<long long*>(part.data_ptr<int64_t>()), cur_stream()),
+        "rank_scan");
+  out.select(1, 0).copy_(total);
+  out.select(1, 1).copy_(t.select(1, 0));
+  out.narrow(1, 2, 4).copy_(part.sum(1));
+  return out;
+}
+
+// Last-layer Laplace (uq_laplace.hip).  laplace_gram: flat fp64 [(D+1)^2 H | (D+1) g | loglik | n_valid] of phi (n, D)
+// fp32, theta (D+1) fp64 and y (n) uint8.  range_len (windows per range, ops/laplace.py:range_len) fixes the order of
+// the fp64 additions; grid (0: one workgroup per range) does not change the result.  Limits: D + 1 <= 128 and the
+// range partials stay within 64 MB.
+at::Tensor laplace_gram(const at::Tensor& phi, const at::Tensor& theta, const at::Tensor& y, int64_t range_len,
+                        int64_t grid) {
+  TORCH_CHECK(phi.is_cuda() && phi.scalar_type() == at::kFloat && phi.dim() == 2,
+              "laplace_gram: phi must be (n, D) fp32 on the GPU");
+  const int64_t n = phi.size(0), D = phi.size(1);
+  TORCH_CHECK(D >= 1 && D + 1 <= apneauq::laplace_max_dp(), "laplace_gram: D + 1 must be in 2..128");
+  TORCH_CHECK(theta.is_cuda() && theta.scalar_type() == at::kDouble && theta.dim() == 1 && theta.size(0) == D + 1,
+              "laplace_gram: theta must be (D + 1,) fp64 on the GPU");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kByte && y.dim() == 1 && y.size(0) == n,
+              "laplace_gram: y must be (n,) uint8 on the GPU");
+  TORCH_CHECK(range_len >= 1 && grid >= 0 && grid < (int64_t(1) << 20), "laplace_gram: bad range_len / grid");
+  const int64_t n_ranges = (n + range_len - 1) / range_len;
+  const int64_t pd = apneauq::laplace_part_doubles((int)D);
+  TORCH_CHECK(n_ranges * pd * 8 <= (int64_t(64) << 20), "laplace_gram: the range partials must stay within 64 MB");
+  auto pp = phi.contiguous(), tt = theta.contiguous(), yy = y.contiguous();
+  const at::DeviceGuard guard(pp.device());
+  auto part = at::empty({std::max<int64_t>(n_ranges, 1) * pd}, tt.options());
+  auto out = at::empty({(D + 1) * (D + 1) + (D + 1) + 2}, tt.options());
+  check(apneauq::launch_laplace_gram(pp.data_ptr<float>(), tt.data_ptr<double>(), yy.data_ptr<uint8_t>(), (long long)n,
+                                     (int)D, (long long)range_len, (int)grid, part.data_ptr<double>(),
+                                     out.data_ptr<double>(), cur_stream()),
+        "laplace_gram");
+  return out;
+}
+
+// laplace_predict: mx (D+1, 1 + T + D+1) fp64 = [theta | theta_1 .. theta_T | L] -> preds (T, n) fp32 and the moments
+// (3, n) fp64: mean logit, logit variance, probit probability.  NaN for a window with a non-finite feature.
+std::tuple<at::Tensor, at::Tensor> laplace_predict(const at::Tensor& phi, const at::Tensor& mx, int64_t T) {
+  TORCH_CHECK(phi.is_cuda() && phi.scalar_type() == at::kFloat && phi.dim() == 2,
+              "laplace_predict: phi must be (n, D) fp32 on the GPU");
+  const int64_t n = phi.size(0), D = phi.size(1);
+  TORCH_CHECK(D >= 1 && D + 1 <= apneauq::laplace_max_dp(), "laplace_predict: D + 1 must be in 2..128");
+  TORCH_CHECK(T >= 0 && T < (int64_t(1) << 24), "laplace_predict: T must be in 0..2^24");
+  TORCH_CHECK(mx.is_cuda() && mx.scalar_type() == at::kDouble && mx.dim() == 2 && mx.size(0) == D + 1 &&
+                  mx.size(1) == T + D + 2,
+              "laplace_predict: mx must be (D + 1, T + D + 2) fp64 on the GPU");
+  auto pp = phi.contiguous(), mm = mx.contiguous();
+  const at::DeviceGuard guard(pp.device());
+  auto preds = at::empty({T, n}, pp.options());
+  auto mom = at::empty({3, n}, mm.options());
+  if (n == 0) return std::make_tuple(preds, mom);
+  double* mp = mom.data_ptr<double>();
+  check(apneauq::launch_laplace_predict(pp.data_ptr<float>(), mm.data_ptr<double>(), (long long)n, (int)D, (int)T,
+                                        preds.data_ptr<float>(), mp, mp + n, mp + 2 * n, cur_stream()),
+        "laplace_predict");
+  return std::make_tuple(preds, mom);
+}
+
+// Pass / member-count convergence (uq_converge.hip): (R, K, 11) int64 sums over the windows of the metrics of
+// the first counts[k] passes of orders[r].  Limits: T <= 128 (the tile's planes fit LDS), K <= 32, R <= 4096 and
+// n <= 2^22 per launch (a fixed-point term is at most 2^40, so every sum stays below 2^62; the front end splits
+// larger sets and adds).  The kernel clamps the pass indices to [0, T); ops/converge.py checks orders and counts.
+at::Tensor converge(const at::Tensor& probs, const at::Tensor& y, const at::Tensor& orders, const at::Tensor& counts,
+                    int64_t rep_groups) {
+  TORCH_CHECK(probs.is_cuda() && probs.scalar_type() == at::kFloat && probs.dim() == 2,
+              "converge: probs must be a (T, n) float32 GPU tensor");
+  const int64_t t_count = probs.size(0), n = probs.size(1);
+  TORCH_CHECK(t_count >= 1 && t_count <= 128, "converge: T must be in 1..128");
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 22), "converge: n must be in 1..2^22");
+  TORCH_CHECK(orders.is_cuda() && orders.scalar_type() == at::kInt && orders.dim() == 2 && orders.size(1) == t_count,
+              "converge: orders must be (R, T) int32 on the GPU");
+  const int64_t n_rep = orders.size(0);
+  TORCH_CHECK(n_rep >= 1 && n_rep <= 4096, "converge: R must be in 1..4096");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == at::kInt && counts.dim() == 1,
+              "converge: counts must be (K,) int32 on the GPU");
+  const int64_t n_cnt = counts.size(0);
+  TORCH_CHECK(n_cnt >= 1 && n_cnt <= 32, "converge: K must be in 1..32");
+  TORCH_CHECK(rep_groups >= 1 && rep_groups <= 1024, "converge: rep_groups must be in 1..1024");
+  auto pp = probs.contiguous(), oo = orders.contiguous(), cc = counts.contiguous();
+  auto yy = y.to(at::kInt).contiguous();
+  TORCH_CHECK(yy.is_cuda() && yy.dim() == 1 && yy.size(0) == n, "converge: y must be (n,) on the GPU");
+  const at::DeviceGuard guard(pp.device());
+  auto out = at::zeros({n_rep, n_cnt, 11}, pp.options().dtype(at::kLong));
+  check(apneauq::launch_converge(pp.data_ptr<float>(), yy.data_ptr<int>(), oo.data_ptr<int>(), cc.data_ptr<int>(),
+                                 (int)t_count, (int)n, (int)n_rep, (int)n_cnt, (int)rep_groups,
+                                 reinterpret_cast<long long*>(out.data_ptr<int64_t>()), cur_stream()),
+        "converge");
+  return out;
+}
+
+}  // namespace
+
+TORCH_LIBRARY_FRAGMENT(apneauq, m) {
+  m.def("uq_reduce(Tensor probs) -> Tensor");
+  m.def("bootstrap(Tensor metrics, Tensor y, Tensor? idx, int seed, int n_boot) -> Tensor");
+  m.def("bootstrap_partial(Tensor metrics, Tensor y, Tensor? idx, int seed, int n_boot, int n_global, int lo) -> Tensor");
+  m.def("calib_prep(Tensor p, Tensor score, Tensor y, Tensor thr, int n_bins) -> Tensor");
+  m.def("calib_bootstrap(Tensor rec, Tensor? idx, int seed, int n_boot, int n_global, int lo, int n_bins, int n_thr, int slices) -> Tensor");
+  m.def("patient_reduce(Tensor probs, Tensor m, Tensor y, Tensor code, int n_pat) -> (Tensor, Tensor)");
+  m.def("patient_bootstrap(Tensor prec, Tensor? idx, int seed, int n_boot) -> Tensor");
+  m.def("rank_count(Tensor pos, Tensor? idx, int seed, int b0, int n_boot, int n_sorted) -> Tensor");
+  m.def("rank_scan(Tensor w, Tensor packed, Tensor bounds) -> Tensor");
+  m.def("laplace_gram(Tensor phi, Tensor theta, Tensor y, int range_len, int grid) -> Tensor");
+  m.def("laplace_predict(Tensor phi, Tensor mx, int T) -> (Tensor, Tensor)");
+  m.def("converge(Tensor probs, Tensor y, Tensor orders, Tensor counts, int rep_groups) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
+  m.impl("uq_reduce", &uq_reduce);
+  m.impl("bootstrap", &bootstrap);
+  m.impl("bootstrap_partial", &bootstrap_partial);
+  m.impl("calib_prep", &calib_prep);
+  m.impl("calib_bootstrap", &calib_bootstrap);
+  m.impl("patient_reduce", &patient_reduce);
+  m.impl("patient_bootstrap", &patient_bootstrap);
+  m.impl("rank_count", &rank_count);
+  m.impl("rank_scan", &rank_scan);
+  m.impl("laplace_gram", &laplace_gram);
+  m.impl("laplace_predict", &laplace_predict);
+  m.impl("converge", &converge);
+}

@@ -10,6 +10,7 @@
 //
 // The scale constants and the code-word layout are mirrored in ops/calib.py (the eager emulation).
 #include "common.h"
+#include "uq_api.h"
 
 namespace apneauq {
 
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(kCalibThreads) void calib_bootstrap_kernel(const in
   __syncthreads();
   CalibWaveHist& h = hist[wave];
   unsigned long long s_brier = 0ull, s_nll = 0ull;
-  const unsigned bkey = mix32(seed ^ mix32((unsigned)b * 0x9E3779B9u + 0x7F4A7C15u));
+  const unsigned bkey = boot_key(seed, (unsigned)b);
   const long long j0 = (long long)g * n / n_slice, j1 = (long long)(g + 1) * n / n_slice;
   const int* idx_b = idx ? idx + (long long)b * n : nullptr;
   for (long long jb = j0 + threadIdx.x; jb < j1; jb += (long long)kCalibUnroll * kCalibThreads) {
@@ -101,8 +102,7 @@ __global__ __launch_bounds__(kCalibThreads) void calib_bootstrap_kernel(const in
         if (idx_b) {
           raw = (unsigned)idx_b[j];
         } else {
-          const unsigned hsh = mix32(bkey ^ mix32((unsigned)j));
-          raw = (unsigned)(((unsigned long long)hsh * (unsigned long long)n) >> 32);
+          raw = boot_draw(bkey, (unsigned)j, n);
         }
       }
       k[u] = raw - (unsigned)lo;

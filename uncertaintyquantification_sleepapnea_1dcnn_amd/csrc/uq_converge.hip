@@ -10,6 +10,7 @@
 // The scale constant, the column layout and the limits are mirrored in ops/converge.py (the eager
 // emulation).
 #include "common.h"
+#include "uq_api.h"
 
 namespace apneauq {
 

@@ -23,6 +23,7 @@
 // only, ops/laplace.py range_len); a range is accumulated in window order by whichever workgroup takes it, into
 // its own partial; laplace_gram_reduce adds the partials in range order.  No floating-point atomics.
 #include "common.h"
+#include "uq_api.h"
 
 namespace apneauq {
 

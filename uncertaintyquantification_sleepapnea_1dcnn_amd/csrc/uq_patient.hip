@@ -11,6 +11,7 @@
 //
 // The scale constants and the column layouts are mirrored in ops/patient.py (the eager emulation).
 #include "common.h"
+#include "uq_api.h"
 
 namespace apneauq {
 
@@ -184,15 +185,14 @@ __global__ __launch_bounds__(kPatThreads) void patient_bootstrap_kernel(const lo
   long long acc[kPatFields];
 #pragma unroll
   for (int f = 0; f < kPatFields; ++f) acc[f] = 0;
-  const unsigned bkey = mix32(seed ^ mix32((unsigned)b * 0x9E3779B9u + 0x7F4A7C15u));
+  const unsigned bkey = boot_key(seed, (unsigned)b);
   const int* idx_b = idx ? idx + (long long)b * n_pat : nullptr;
   for (int j = threadIdx.x; j < n_pat; j += kPatThreads) {
     unsigned k;
     if (idx_b) {
       k = (unsigned)idx_b[j];
     } else {
-      const unsigned hsh = mix32(bkey ^ mix32((unsigned)j));
-      k = (unsigned)(((unsigned long long)hsh * (unsigned long long)n_pat) >> 32);
+      k = boot_draw(bkey, (unsigned)j, n_pat);
     }
     if (k >= (unsigned)n_pat) continue;
     const long long* r = prec + (long long)k * kPatFields;

@@ -29,6 +29,7 @@
 // scale 2^56 (ops/rank.py S_BITS) keeps the quantisation n 2^-57 <= 1e-9 at n = 2^27 and the sum (the terms
 // add up to at most 1) at 2^56.
 #include "common.h"
+#include "uq_api.h"
 
 namespace apneauq {
 
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(kCountThreads) void rank_count_kernel(const int* __
                                                                    int* __restrict__ w) {
   const int b = blockIdx.x;
   APNEAUQ_DASSERT(blockDim.x == kCountThreads && n_draw > 0 && n_sorted >= 0 && stride >= n_sorted);
-  const unsigned bkey = mix32(seed ^ mix32((unsigned)(b0 + b) * 0x9E3779B9u + 0x7F4A7C15u));
+  const unsigned bkey = boot_key(seed, (unsigned)(b0 + b));
   const int* idx_b = idx ? idx + (long long)b * n_draw : nullptr;
   int* w_b = w + (long long)b * stride;
   const long long step = (long long)gridDim.y * kCountThreads * kCountUnroll;
@@ -69,8 +70,7 @@ __global__ __launch_bounds__(kCountThreads) void rank_count_kernel(const int* __
         if (idx_b) {
           raw[u] = (unsigned)idx_b[j];
         } else {
-          const unsigned hsh = mix32(bkey ^ mix32((unsigned)j));
-          raw[u] = (unsigned)(((u64)hsh * (u64)n_draw) >> 32);
+          raw[u] = boot_draw(bkey, (unsigned)j, n_draw);
         }
       }
     }

@@ -26,6 +26,7 @@
 // ops/recal.py range_len); a range is accumulated in tile order by whichever workgroup takes it and stored with
 // plain stores into its own partial; recal_reduce adds the partials in range order.  No floating-point atomics.
 #include "common.h"
+#include "uq_api.h"
 
 namespace apneauq {
 

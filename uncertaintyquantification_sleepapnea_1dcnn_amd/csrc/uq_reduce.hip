@@ -12,6 +12,7 @@
 //            each of B resamples.  The per-window metrics do not change under resampling, so every
 //            replicate is a gather + masked mean; one workgroup per replicate, fp64 accumulation.
 #include "common.h"
+#include "uq_api.h"
 
 namespace apneauq {
 
@@ -96,14 +97,14 @@ __global__ __launch_bounds__(kBootThreads) void bootstrap_kernel(const float* __
   const float* mi = metrics + kMI * (long long)ld;
   double acc[7] = {0, 0, 0, 0, 0, 0, 0};  // sum var, sum var|0, cnt0, sum var|1, cnt1, sum H, sum EH  (+MI below)
   double smi = 0.0;
-  const unsigned bkey = mix32(seed ^ mix32((unsigned)b * 0x9E3779B9u + 0x7F4A7C15u));
+  const unsigned bkey = boot_key(seed, (unsigned)b);
   for (int j = threadIdx.x; j < n; j += kBootThreads) {
     int k;
     if (idx) {
       k = idx[(long long)b * n + j];
     } else {
-      const unsigned hsh = mix32(bkey ^ mix32((unsigned)j));
-      k = (int)(((unsigned long long)hsh * (unsigned long long)n) >> 32);
+      const unsigned r = boot_draw(bkey, (unsigned)j, n);
+      k = (int)r;
     }
     if constexpr (PARTIAL) {
       k -= lo;

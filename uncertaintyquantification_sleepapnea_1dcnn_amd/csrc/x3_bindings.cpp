@@ -1,41 +1,15 @@
 // torch.library registration of the fp32-faithful (fp16x3) layer-wise inference kernels
 // (x3_layers.hip): torch.ops.apneauq.x3_*.  Host C++; shapes are checked here against what the
 // kernels and their grids assume before anything is launched.
-#include <ATen/ATen.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/library.h>
-
-#include <hip/hip_runtime_api.h>
-
-#include "x3_args.h"
+#include "arch_tables.h"
+#include "bind_util.h"
+#include "x3_api.h"
 #include "x3_dense_map.h"
 
-namespace apneauq {
-int x3_lds_bytes(int layer);
-int x3_tile_samples(int layer);
-int x3_wg_per_cu(int layer);
-bool x3_has_dense(int layer);
-hipError_t x3_launch_layer(int layer, const x3::LayerArgs& A, int grid, bool dense_rows, hipStream_t stream);
-hipError_t x3_launch_l1(const x3::L1Args& A, hipStream_t stream);
-hipError_t x3_launch_aff(const x3::AffArgs& A, hipStream_t stream);
-hipError_t x3_launch_head(const x3::HeadArgs& A, hipStream_t stream);
-}  // namespace apneauq
-
 namespace {
-
-constexpr int kCh[7] = {4, 128, 192, 224, 96, 256, 96};
-constexpr int kKs[6] = {7, 5, 3, 7, 9, 9};
-
-inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
-inline void check(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, " failed: ", hipGetErrorString(e)); }
-
-inline void need(const at::Tensor& t, at::ScalarType dt, int64_t min_numel, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous(), what, ": contiguous GPU tensor of dtype ", dt,
-              " required");
-  TORCH_CHECK(t.numel() >= min_numel, what, ": ", t.numel(), " elements, need >= ", min_numel);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, ": 16-B alignment required");
-}
+using namespace apneauq::bind;
+constexpr auto& kCh = apneauq::arch::C;
+constexpr auto& kKs = apneauq::arch::KS;
 
 int num_cus(const at::Tensor& t) {
   int n = 0;

@@ -58,7 +58,7 @@
 //     ahead), activations the B operand (LDS).  Waves tile rows x output channels (WM x WN) per layer so
 //     that each weight fragment is re-read by at most WM waves of the 256-row tile.
 #include "common.h"
-#include "x3_args.h"
+#include "x3_api.h"
 #include "x3_dense_map.h"
 
 namespace apneauq {

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _ext
-from .rng import _mix32_t, mix32_int
+from .rng import boot_row
 
 # fixed-point scales shared with the kernels (uq_calib.hip kCalibPScale / kCalibNllScale)
 P_BITS = 30
@@ -106,9 +106,7 @@ def prep(p: torch.Tensor, score: torch.Tensor, y: torch.Tensor, thr: torch.Tenso
 
 def _hash_row(n: int, b: int, seed: int, device) -> torch.Tensor:
     """Row b of ``ops.uq._hash_idx(n, B, seed)`` without the other rows."""
-    bkey = mix32_int((seed & 0xFFFFFFFF) ^ mix32_int((b * 0x9E3779B9 + 0x7F4A7C15) & 0xFFFFFFFF))
-    j = torch.arange(n, device=device, dtype=torch.int64)
-    return (_mix32_t(bkey ^ _mix32_t(j)) * n) >> 32
+    return boot_row(n, b, seed, device)
 
 
 def bootstrap_sums_eager(rec: torch.Tensor, idx: Optional[torch.Tensor], seed: int, n_boot: int, n_global: int,

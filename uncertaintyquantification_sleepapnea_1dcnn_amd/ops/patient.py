@@ -33,7 +33,7 @@ import torch
 
 from . import _ext
 from . import uq as uq_ops
-from .calib import _hash_row
+from .rng import boot_row
 
 # shared with the kernels (uq_patient.hip kPatScale / kPatClamp / kPatRec / kPatFields)
 Q_BITS = 30
@@ -125,7 +125,7 @@ def bootstrap_sums_eager(prec: torch.Tensor, idx: Optional[torch.Tensor], seed: 
     cell = (prec[:, TRUE_CLASS] & 3) * N_CLASS + (prec[:, PRED_CLASS] & 3)
     out = torch.zeros(n_boot, N_SUMS, dtype=torch.int64, device=dev)
     for b in range(n_boot):
-        k = _hash_row(n_pat, b, seed, dev) if idx is None else idx[b].long().to(dev)
+        k = boot_row(n_pat, b, seed, dev) if idx is None else idx[b].long().to(dev)
         k = k[(k >= 0) & (k < n_pat)]
         out[b, :N_PREC] = prec[k].sum(0)
         out[b, N_PREC:] = torch.bincount(cell[k], minlength=N_CLASS * N_CLASS)

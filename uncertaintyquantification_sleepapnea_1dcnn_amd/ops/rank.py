@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _ext
-from .calib import _hash_row
+from .rng import boot_row
 
 COLS = ("W", "P", "U2", "groups", "prauc_q", "ap_q")
 W_COL, P_COL, U2_COL, GROUPS_COL, PRAUC_COL, AP_COL = range(6)
@@ -124,7 +124,7 @@ def weights_eager(pos: torch.Tensor, n_sorted: int, n_boot: int, idx: Optional[t
     out = torch.zeros(n_boot, n_sorted, dtype=torch.int32, device=dev)
     p = pos.long()
     for b in range(n_boot):
-        draws = _hash_row(n, b0 + b, seed, dev) if idx is None else idx[b].long().to(dev)
+        draws = boot_row(n, b0 + b, seed, dev) if idx is None else idx[b].long().to(dev)
         k = p[draws[(draws >= 0) & (draws < n)]]
         k = k[(k >= 0) & (k < n_sorted)]
         out[b] = torch.bincount(k, minlength=n_sorted).to(torch.int32)

@@ -88,6 +88,20 @@ def _mix32_t(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def boot_draw(seed: int, b: torch.Tensor, j: torch.Tensor, n: int) -> torch.Tensor:
+    """Item drawn as draw ``j`` of bootstrap replicate ``b`` over ``n`` items (int64 tensors, broadcast):
+    the one host definition of the device draw (``csrc/common.h`` ``boot_key`` / ``boot_draw``), so the same
+    seed gives the same resamples in every kernel, every eager emulation and on every shard."""
+    bkey = _mix32_t((seed & _M32) ^ _mix32_t((b * 0x9E3779B9 + 0x7F4A7C15) & _M32))
+    return (_mix32_t(bkey ^ _mix32_t(j)) * n) >> 32
+
+
+def boot_row(n: int, b: int, seed: int, device) -> torch.Tensor:
+    """The ``n`` draws of replicate ``b`` alone."""
+    j = torch.arange(n, device=device, dtype=torch.int64)
+    return boot_draw(seed, torch.tensor(b, device=device, dtype=torch.int64), j, n)
+
+
 def keep_mask_torch(key: int, samples: torch.Tensor, length: int, channels: int, rate: float) -> torch.Tensor:
     """Boolean keep-mask (len(samples), length, channels) on ``samples.device``."""
     dev = samples.device

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import os
 import struct
-from typing import Callable, List, Optional
+from typing import Callable, Dict, List, Optional
 
 import numpy as np
 import torch
@@ -48,6 +48,17 @@ def supports(spec: ModelSpec) -> bool:
 
 def _fbits(x: float) -> int:
     return struct.unpack("<I", struct.pack("<f", float(x)))[0]
+
+
+def pack_ctx(fields: Dict[str, int]) -> torch.Tensor:
+    """The int64 CPU ctx tensor of ``train_call``: ``fields`` (one integer per name -- a device pointer, a
+    scalar or a float's bit pattern) in the order of ``torch.ops.apneauq.train_ctx_fields()``, the field list
+    the kernels' argument struct and its decoder are generated from (``csrc/train_ctx.h``)."""
+    names = list(_ext.ops().train_ctx_fields())
+    unknown = sorted(set(fields) - set(names))
+    if unknown:
+        raise ValueError(f"train ctx: unknown field {unknown[0]!r}")
+    return torch.tensor([fields[n] for n in names], dtype=torch.int64)  # KeyError names a missing field
 
 
 def padded_rows(n_samples: int) -> int:
@@ -153,29 +164,29 @@ class TrainWorkspace:
         if key == self._ctx_key:
             return self.ctx
         spec, v, g = self.model.spec, self.model.store.views, self.gviews
-        vals: List[int] = []
+        f: Dict[str, int] = {}
         for l in range(6):
             i = l + 1
             p = spec.blocks[l].dropout
-            vals += [self.wf[l].data_ptr(), self.wd[l].data_ptr(), v[f"conv1d_{i}/bias"].data_ptr(),
-                     v[f"batchnorm_{i}/gamma"].data_ptr(), v[f"batchnorm_{i}/beta"].data_ptr(),
-                     v[f"batchnorm_{i}/moving_mean"].data_ptr(), v[f"batchnorm_{i}/moving_variance"].data_ptr(),
-                     g[f"conv1d_{i}/kernel"].data_ptr(), g[f"conv1d_{i}/bias"].data_ptr(),
-                     g[f"batchnorm_{i}/gamma"].data_ptr(), g[f"batchnorm_{i}/beta"].data_ptr(),
-                     self.R[l].data_ptr(), self.dY[l].data_ptr(), self.st[l].data_ptr(), self.bst[l].data_ptr(),
-                     rng.dropout_threshold(p), _fbits(1.0 / (1.0 - p) if p < 1 else 0.0), self.dZ[l].data_ptr()]
-        vals += [self.x.data_ptr(), self.y.data_ptr(), v["output_layer/kernel"].data_ptr(),
-                 v["output_layer/bias"].data_ptr(), g["output_layer/kernel"].data_ptr(),
-                 g["output_layer/bias"].data_ptr(), self.logits.data_ptr(), self.dlogit.data_ptr(),
-                 self.loss.data_ptr(), n, n_win, groups, TRAIN_PASS_BASE, window_offset,
-                 int(seed) & ((1 << 63) - 1), int(bool(dropout)), _fbits(inv_count), _fbits(inv_batch),
-                 _fbits(spec.bn_epsilon), _fbits(spec.bn_momentum),
-                 self.counters.data_ptr() if device_counters else 0, self.groups, int(self.shared0),
-                 self.wpart.data_ptr() if self.wpart is not None else 0,
-                 self.det.data_ptr() if self.det is not None else 0,
-                 self.tab.data_ptr() if table else 0,
-                 self.hpart.data_ptr() if (self.hpart is not None and self.det is None) else 0]
-        self.ctx = torch.tensor(vals, dtype=torch.int64)
+            layer = dict(wf=self.wf[l], wd=self.wd[l], bias=v[f"conv1d_{i}/bias"], gamma=v[f"batchnorm_{i}/gamma"],
+                         beta=v[f"batchnorm_{i}/beta"], mmean=v[f"batchnorm_{i}/moving_mean"],
+                         mvar=v[f"batchnorm_{i}/moving_variance"], gw=g[f"conv1d_{i}/kernel"], gb=g[f"conv1d_{i}/bias"],
+                         ggamma=g[f"batchnorm_{i}/gamma"], gbeta=g[f"batchnorm_{i}/beta"], R=self.R[l], dY=self.dY[l],
+                         dZ=self.dZ[l], st=self.st[l], bst=self.bst[l])
+            f.update({f"L{l}.{k}": t.data_ptr() for k, t in layer.items()})
+            f[f"L{l}.thr"] = rng.dropout_threshold(p)
+            f[f"L{l}.dsc"] = _fbits(1.0 / (1.0 - p) if p < 1 else 0.0)
+        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        f.update(x=ptr(self.x), y=ptr(self.y), dense_w=ptr(v["output_layer/kernel"]), dense_b=ptr(v["output_layer/bias"]),
+                 g_dense_w=ptr(g["output_layer/kernel"]), g_dense_b=ptr(g["output_layer/bias"]), logits=ptr(self.logits),
+                 dlogit=ptr(self.dlogit), loss_sum=ptr(self.loss), B=n, n_win=n_win, groups=groups,
+                 pass_base=TRAIN_PASS_BASE, window_offset=window_offset, seed=int(seed) & ((1 << 63) - 1),
+                 dropout=int(bool(dropout)), inv_count=_fbits(inv_count), inv_batch=_fbits(inv_batch),
+                 eps=_fbits(spec.bn_epsilon), momentum=_fbits(spec.bn_momentum),
+                 pass_dev=ptr(self.counters if device_counters else None), st_groups=self.groups,
+                 wpart=ptr(self.wpart), det=ptr(self.det), shared0=int(self.shared0), tab=ptr(self.tab if table else None),
+                 hpart=ptr(self.hpart if self.det is None else None))
+        self.ctx = pack_ctx(f)
         self._ctx_key = key
         return self.ctx
 

@@ -51,13 +51,11 @@ def metrics(probs: torch.Tensor) -> torch.Tensor:
 
 
 def _hash_idx(n: int, n_boot: int, seed: int, device) -> torch.Tensor:
-    from .rng import _mix32_t
+    from .rng import boot_draw
 
     b = torch.arange(n_boot, device=device, dtype=torch.int64)[:, None]
     j = torch.arange(n, device=device, dtype=torch.int64)[None, :]
-    bkey = _mix32_t(torch.full_like(b, seed & 0xFFFFFFFF) ^ _mix32_t((b * 0x9E3779B9 + 0x7F4A7C15) & 0xFFFFFFFF))
-    h = _mix32_t(bkey ^ _mix32_t(j))
-    return (h * n) >> 32
+    return boot_draw(seed, b, j, n)
 
 
 def bootstrap_eager(m: torch.Tensor, y: torch.Tensor, idx: Optional[torch.Tensor], seed: int, n_boot: int) -> torch.Tensor:
