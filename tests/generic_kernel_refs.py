@@ -29,6 +29,11 @@ def f64(t):
     return t.detach().cpu().double()
 
 
+def d64(t):
+    """As :func:`f64`, on the tensor's own device (references computed next to the kernels' outputs)."""
+    return t.detach().double()
+
+
 def f32r(t):
     """float64 tensor rounded once to fp32 (and back): what a kernel reads from an fp32 buffer."""
     return t.float().double()
@@ -40,18 +45,18 @@ def stored(t, bf16):
 
 
 # ------------------------------------------------------------------------------------------ convolution
-def conv64(x, w, b=None, relu=False):
-    """(N, L, Cin) x (k, Cin, Cout) 'same' conv in float64 (odd k)."""
-    xt = f64(x).permute(0, 2, 1)
-    wt = f64(w).permute(2, 1, 0)
-    y = torch.nn.functional.conv1d(xt, wt, None if b is None else f64(b), padding=(w.shape[0] - 1) // 2)
+def conv64(x, w, b=None, relu=False, to=f64):
+    """(N, L, Cin) x (k, Cin, Cout) 'same' conv in float64 (odd k).  ``to``: :func:`f64` (CPU) or :func:`d64`."""
+    xt = to(x).permute(0, 2, 1)
+    wt = to(w).permute(2, 1, 0)
+    y = torch.nn.functional.conv1d(xt, wt, None if b is None else to(b), padding=(w.shape[0] - 1) // 2)
     y = y.permute(0, 2, 1)
     return torch.relu(y) if relu else y
 
 
-def conv_abs64(x, w, b=None):
+def conv_abs64(x, w, b=None, to=f64):
     """The abs-sum companion: sum of the absolute terms of every output entry."""
-    return conv64(f64(x).abs(), f64(w).abs(), None if b is None else f64(b).abs())
+    return conv64(to(x).abs(), to(w).abs(), None if b is None else to(b).abs(), to=to)
 
 
 def flip_t(w):
@@ -248,9 +253,9 @@ def dz_allow(ref, mag, bf16):
 
 
 # ------------------------------------------------------------------------------------------ wgrad / head
-def wgrad64(xp, dzp, R, k):
+def wgrad64(xp, dzp, R, k, to=f64):
     """gw[tap] = xp[tap : tap + R].T @ dzp[:R] -> (gw (k, cin, cout), the same over absolute values)."""
-    xp, dzp = f64(xp), f64(dzp)[:R]
+    xp, dzp = to(xp), to(dzp)[:R]
     gw = torch.stack([xp[t: t + R].t() @ dzp for t in range(k)])
     ab = torch.stack([xp[t: t + R].abs().t() @ dzp.abs() for t in range(k)])
     return gw, ab

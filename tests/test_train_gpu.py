@@ -64,6 +64,7 @@ def test_hip_train_step_matches_autograd(n):
         # tight vs the bf16-dataflow emulation, direction-only vs fp32 autograd (BN-backward
         # cancellation turns bf16 quantisation into ~10-20 % relative noise, see train_emulation.py)
         e = _rel(hip, em_grad[name].reshape(-1))
+        print(f"[step n={n}] {name}: {e:.4f}")
         assert e < 0.12, (name, e)
         cos = torch.nn.functional.cosine_similarity(hip, ref_grad[off: off + k], dim=0).item()
         assert cos > 0.97, (name, cos)

@@ -128,9 +128,9 @@ __device__ __forceinline__ void bn_moments(const Args& A, int l, int g, int c, f
   const int gg = stat_group(A, l, g);
   const double s1 = slot_sumd(A.L[l].st + (gg * 2 + 0) * Cc + c, ss);
   const double s2 = slot_sumd(A.L[l].st + (gg * 2 + 1) * Cc + c, ss);
-  const double m = s1 * (double)A.inv_count;
+  const double m = s1 * A.inv_count;
   mu = (float)m;
-  var = (float)fmax(s2 * (double)A.inv_count - m * m, 0.0);
+  var = (float)fmax(s2 * A.inv_count - m * m, 0.0);
 }
 
 // Per-channel BN affine of block l for stats group g, into LDS: s[c], t[c], mean[c], rstd[c].
@@ -186,8 +186,8 @@ __device__ __forceinline__ void tab_write_bwd(const Args& A, int l) {
   const int Cc = C[l + 1], c = threadIdx.x;
   if (c >= Cc) return;
   float* t = A.tab + l * kTabRows * 256;
-  t[kTabMdy * 256 + c] = (float)(slot_sumd(A.L[l].bst + c, 2 * Cc) * (double)A.inv_count);
-  t[kTabMdyx * 256 + c] = (float)(slot_sumd(A.L[l].bst + Cc + c, 2 * Cc) * (double)A.inv_count);
+  t[kTabMdy * 256 + c] = (float)(slot_sumd(A.L[l].bst + c, 2 * Cc) * A.inv_count);
+  t[kTabMdyx * 256 + c] = (float)(slot_sumd(A.L[l].bst + Cc + c, 2 * Cc) * A.inv_count);
 }
 
 __device__ __forceinline__ unsigned layer_sample_key(const Args& A, int l, int sample) {
@@ -203,7 +203,7 @@ struct TabBwd {  // backward rows of one block's parameter table entry (wgrad_re
   float* mdy;
   float* mdyx;
   int cc;
-  float inv_count;
+  double inv_count;
 };
 // One layer's wgrad partial reduction, run as a side job of another launch (single-device steps:
 // dgrad<l-1> reduces wgrad<l>'s partials for l = 2..5, step_reduce_kernel those of wgrad<1> and wgrad<0>
@@ -268,8 +268,8 @@ __device__ __forceinline__ void wgrad_reduce_cols(const RedJob& jb, int bx, int 
 __device__ __forceinline__ void tab_bwd_rows(const TabBwd& tb) {
   const int c = threadIdx.x;
   if (c < tb.cc) {
-    tb.mdy[c] = (float)(slot_sumd(tb.bst + c, 2 * tb.cc) * (double)tb.inv_count);
-    tb.mdyx[c] = (float)(slot_sumd(tb.bst + tb.cc + c, 2 * tb.cc) * (double)tb.inv_count);
+    tb.mdy[c] = (float)(slot_sumd(tb.bst + c, 2 * tb.cc) * tb.inv_count);
+    tb.mdyx[c] = (float)(slot_sumd(tb.bst + tb.cc + c, 2 * tb.cc) * tb.inv_count);
   }
 }
 

@@ -12,8 +12,8 @@ using namespace apneauq::bind;
 // ctx: int64 CPU tensor of device pointers / scalars built once per workspace (ops/train_ops.py pack_ctx): one slot
 // per field of the two lists in train_ctx.h, in list order -- the six layers' fields, then the launch-wide ones
 #define CTX_ONE(...) +1
-constexpr int kCtxLayer = 0 APNEAUQ_TRAIN_LAYER_FIELDS(CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE);
-constexpr int kCtxLen = 6 * kCtxLayer APNEAUQ_TRAIN_ARGS_FIELDS(CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE);
+constexpr int kCtxLayer = 0 APNEAUQ_TRAIN_LAYER_FIELDS(CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE);
+constexpr int kCtxLen = 6 * kCtxLayer APNEAUQ_TRAIN_ARGS_FIELDS(CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE, CTX_ONE);
 
 float bits_to_float(int64_t v) {
   uint32_t u = static_cast<uint32_t>(v);
@@ -22,16 +22,22 @@ float bits_to_float(int64_t v) {
   return f;
 }
 
+double bits_to_double(int64_t v) {
+  double d;
+  std::memcpy(&d, &v, 8);
+  return d;
+}
+
 #define CTX_NAME_P(T, n) v.push_back(pre + #n);
 #define CTX_NAME(n) v.push_back(pre + #n);
 std::vector<std::string> train_ctx_fields() {
   std::vector<std::string> v;
   for (int l = 0; l < 6; ++l) {
     const std::string pre = "L" + std::to_string(l) + ".";
-    APNEAUQ_TRAIN_LAYER_FIELDS(CTX_NAME_P, CTX_NAME, CTX_NAME, CTX_NAME, CTX_NAME)
+    APNEAUQ_TRAIN_LAYER_FIELDS(CTX_NAME_P, CTX_NAME, CTX_NAME, CTX_NAME, CTX_NAME, CTX_NAME)
   }
   const std::string pre;
-  APNEAUQ_TRAIN_ARGS_FIELDS(CTX_NAME_P, CTX_NAME, CTX_NAME, CTX_NAME, CTX_NAME)
+  APNEAUQ_TRAIN_ARGS_FIELDS(CTX_NAME_P, CTX_NAME, CTX_NAME, CTX_NAME, CTX_NAME, CTX_NAME)
   return v;
 }
 
@@ -41,17 +47,18 @@ std::vector<std::string> train_ctx_fields() {
 #define CTX_U(n) S.n = static_cast<unsigned>(*c++);
 #define CTX_Q(n) S.n = static_cast<unsigned long long>(*c++);
 #define CTX_F(n) S.n = bits_to_float(*c++);
+#define CTX_D(n) S.n = bits_to_double(*c++);
 apneauq::train::Args args_from_ctx(const at::Tensor& ctx, int64_t pass_base) {
   TORCH_CHECK(ctx.device().is_cpu() && ctx.scalar_type() == at::kLong && ctx.numel() == kCtxLen,
               "train ctx must be an int64 CPU tensor of length ", kCtxLen);
   const int64_t* c = ctx.data_ptr<int64_t>();
   apneauq::train::Args A;
   for (auto& S : A.L) {
-    APNEAUQ_TRAIN_LAYER_FIELDS(CTX_P, CTX_I, CTX_U, CTX_Q, CTX_F)
+    APNEAUQ_TRAIN_LAYER_FIELDS(CTX_P, CTX_I, CTX_U, CTX_Q, CTX_F, CTX_D)
   }
   {
     auto& S = A;
-    APNEAUQ_TRAIN_ARGS_FIELDS(CTX_P, CTX_I, CTX_U, CTX_Q, CTX_F)
+    APNEAUQ_TRAIN_ARGS_FIELDS(CTX_P, CTX_I, CTX_U, CTX_Q, CTX_F, CTX_D)
   }
   if (pass_base >= 0) A.pass_base = static_cast<unsigned>(pass_base);
   A.bwd_self = 0;

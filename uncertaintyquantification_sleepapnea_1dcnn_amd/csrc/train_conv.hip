@@ -925,12 +925,16 @@ __global__ __launch_bounds__(kThreads) void head_kernel(Args A_, const Args* __r
     const float z = wave_sum(active ? part : 0.f) * (1.0f / kL) + A.dense_b[0];
     if (n < A.B && lane == 0) A.logits[n] = z;
     if (backward && n < A.B) {
-      const float pz = 1.0f / (1.0f + __expf(-z));
+      // e = exp(-|z|) in (0, 1] (expf: __expf rounds z log2(e) first, a relative error of ~|z| 2^-24 in the
+      // result); q = e / (1 + e) is the sigmoid's small side at full relative accuracy, and prob - y comes
+      // from the side that does not cancel (a saturated 1.0f minus a label of 1 is 0 where the gradient is -q)
+      const float e = expf(-fabsf(z));
+      const float q = e / (1.0f + e);
       const float yv = A.y[n];
-      const float dl = (pz - yv) * A.inv_batch;
+      const float dl = (z >= 0.f ? (1.0f - yv) - q : q - yv) * A.inv_batch;
       float* rec = A.det != nullptr ? A.det + (long long)n * kHeadRec : nullptr;  // deterministic mode
       if (lane == 0) {
-        const float loss = fmaxf(z, 0.f) - z * yv + log1pf(__expf(-fabsf(z)));  // BCE on logits
+        const float loss = fmaxf(z, 0.f) - z * yv + log1pf(e);  // BCE on logits
         A.dlogit[n] = dl;
         if (rec != nullptr) {
           rec[0] = loss;
@@ -1164,8 +1168,8 @@ __global__ __launch_bounds__(kThreads, 2) void dgrad_kernel(Args A_, const Args*
       mean[c] = tab_row(A, l, kTabMean)[c];
       rstd[c] = tab_row(A, l, kTabRstd)[c];
       if (l == 5 || A.bwd_self) {  // block 6's backward sums come from the head, no table job in between
-        mdy[c] = (float)(slot_sumd(A.L[l].bst + c, 2 * CIN) * (double)A.inv_count);
-        mdyx[c] = (float)(slot_sumd(A.L[l].bst + CIN + c, 2 * CIN) * (double)A.inv_count);
+        mdy[c] = (float)(slot_sumd(A.L[l].bst + c, 2 * CIN) * A.inv_count);
+        mdyx[c] = (float)(slot_sumd(A.L[l].bst + CIN + c, 2 * CIN) * A.inv_count);
       } else {
         mdy[c] = tab_row(A, l, kTabMdy)[c];
         mdyx[c] = tab_row(A, l, kTabMdyx)[c];
@@ -1190,8 +1194,8 @@ __global__ __launch_bounds__(kThreads, 2) void dgrad_kernel(Args A_, const Args*
       mean[c] = mu;
       rstd[c] = rs;
       gr[c] = Ly.gamma[c] * rs;
-      mdy[c] = (float)(b0 * (double)A.inv_count);
-      mdyx[c] = (float)(b1 * (double)A.inv_count);
+      mdy[c] = (float)(b0 * A.inv_count);
+      mdyx[c] = (float)(b1 * A.inv_count);
     }
     if (c < COUT) {
       mean_prev[c] = mup;
@@ -1391,8 +1395,8 @@ __global__ __launch_bounds__(WgCfg<l>::WAVES * 64, WgCfg<l>::MINB) void wgrad_ke
       mean[c] = tab_row(A, l, kTabMean)[c];
       rstd[c] = tab_row(A, l, kTabRstd)[c];
       if (l == 5 || A.bwd_self) {
-        mdy[c] = (float)(slot_sumd(A.L[l].bst + c, 2 * COUT) * (double)A.inv_count);
-        mdyx[c] = (float)(slot_sumd(A.L[l].bst + COUT + c, 2 * COUT) * (double)A.inv_count);
+        mdy[c] = (float)(slot_sumd(A.L[l].bst + c, 2 * COUT) * A.inv_count);
+        mdyx[c] = (float)(slot_sumd(A.L[l].bst + COUT + c, 2 * COUT) * A.inv_count);
       } else {
         mdy[c] = tab_row(A, l, kTabMdy)[c];
         mdyx[c] = tab_row(A, l, kTabMdyx)[c];
@@ -1418,8 +1422,8 @@ __global__ __launch_bounds__(WgCfg<l>::WAVES * 64, WgCfg<l>::MINB) void wgrad_ke
       mean[c] = mu;
       rstd[c] = rs;
       gr[c] = Ly.gamma[c] * rs;
-      mdy[c] = (float)(b0 * (double)A.inv_count);
-      mdyx[c] = (float)(b1 * (double)A.inv_count);
+      mdy[c] = (float)(b0 * A.inv_count);
+      mdyx[c] = (float)(b1 * A.inv_count);
     }
     if constexpr (!FIRST) {
       if (c < CIN) {

@@ -5,7 +5,7 @@
 // The structs, the decoder of the Python-built ctx (train_bindings.cpp args_from_ctx) and the ctx's name
 // table (torch.ops.apneauq.train_ctx_fields) all expand the two field lists below, in list order: a field
 // is added by adding one line here.  Kinds: P(type, name) device pointer, I int, U unsigned, Q unsigned
-// 64-bit, F float (carried in the int64 ctx as its bit pattern).
+// 64-bit, F float and D double (both carried in the int64 ctx as their bit patterns).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -27,7 +27,7 @@ typedef void frag_t;
 typedef void act_t;
 #endif
 
-#define APNEAUQ_TRAIN_LAYER_FIELDS(P, I, U, Q, F)                                                              \
+#define APNEAUQ_TRAIN_LAYER_FIELDS(P, I, U, Q, F, D)                                                           \
   P(const frag_t, wf)  /* forward fragments  (ksteps, Cout/16, 64, 8) */                                      \
   P(const frag_t, wd)  /* dgrad fragments    (ksteps', Cin/16, 64, 8) */                                      \
   P(const float, bias)                                                                                         \
@@ -63,7 +63,7 @@ typedef void act_t;
 // hpart  training head: per-workgroup dense-weight / loss / dense-bias sums go to [kStatSlots][96 + 2] fp32
 //        slots (workgroup % kStatSlots) that bn_finalize adds in slot order, instead of 256 workgroups'
 //        atomics on the same 98 addresses (nullptr: direct atomics)
-#define APNEAUQ_TRAIN_ARGS_FIELDS(P, I, U, Q, F)                                                               \
+#define APNEAUQ_TRAIN_ARGS_FIELDS(P, I, U, Q, F, D)                                                            \
   P(const act_t, x)    /* PL (rows, 4) */                                                                      \
   P(const float, y)    /* labels (B) */                                                                        \
   P(const float, dense_w)                                                                                      \
@@ -79,8 +79,9 @@ typedef void act_t;
   U(pass_base)         /* dropout pass id of group 0 */                                                        \
   U(window_offset)                                                                                             \
   Q(seed)                                                                                                      \
+  D(inv_count)         /* 1 / (samples per group * 60) -- BN moment normaliser; a double (and next to the */   \
+                       /* 64-bit seed, so the block keeps its size): a float 1/3840 is off by 2^-25 */        \
   I(dropout)                                                                                                   \
-  F(inv_count)         /* 1 / (samples per group * 60) -- BN moment normaliser */                              \
   F(inv_batch)         /* 1 / global batch size -- BCE mean */                                                 \
   F(eps)                                                                                                       \
   F(momentum)                                                                                                  \
@@ -97,14 +98,15 @@ typedef void act_t;
 #define APNEAUQ_DECL_U(n) unsigned n;
 #define APNEAUQ_DECL_Q(n) unsigned long long n;
 #define APNEAUQ_DECL_F(n) float n;
+#define APNEAUQ_DECL_D(n) double n;
 
 struct Layer {
-  APNEAUQ_TRAIN_LAYER_FIELDS(APNEAUQ_DECL_P, APNEAUQ_DECL_I, APNEAUQ_DECL_U, APNEAUQ_DECL_Q, APNEAUQ_DECL_F)
+  APNEAUQ_TRAIN_LAYER_FIELDS(APNEAUQ_DECL_P, APNEAUQ_DECL_I, APNEAUQ_DECL_U, APNEAUQ_DECL_Q, APNEAUQ_DECL_F, APNEAUQ_DECL_D)
 };
 
 struct Args {
   Layer L[6];
-  APNEAUQ_TRAIN_ARGS_FIELDS(APNEAUQ_DECL_P, APNEAUQ_DECL_I, APNEAUQ_DECL_U, APNEAUQ_DECL_Q, APNEAUQ_DECL_F)
+  APNEAUQ_TRAIN_ARGS_FIELDS(APNEAUQ_DECL_P, APNEAUQ_DECL_I, APNEAUQ_DECL_U, APNEAUQ_DECL_Q, APNEAUQ_DECL_F, APNEAUQ_DECL_D)
   int bwd_self;  // dgrad / wgrad launch flag (not in the ctx): sum the backward BN rows of block l from bst[l]
                  // themselves instead of reading the table rows that wgrad_reduce's side job writes -- so a
                  // wgrad chain on a second stream (GraphedTrainStep overlap) carries no dependency back into
@@ -116,11 +118,12 @@ struct Args {
 #undef APNEAUQ_DECL_U
 #undef APNEAUQ_DECL_Q
 #undef APNEAUQ_DECL_F
+#undef APNEAUQ_DECL_D
 
 // The layout every compilation pass (device, hipcc host, the bindings' host compiler) must agree on.
 static_assert(sizeof(Layer) == 136 && sizeof(Args) == 1008, "train::Layer / train::Args layout changed");
 static_assert(__builtin_offsetof(Args, x) == 816 && __builtin_offsetof(Args, seed) == 912 &&
-                  __builtin_offsetof(Args, pass_dev) == 944 && __builtin_offsetof(Args, bwd_self) == 1000,
+                  __builtin_offsetof(Args, inv_count) == 920 && __builtin_offsetof(Args, pass_dev) == 944 && __builtin_offsetof(Args, bwd_self) == 1000,
               "train::Args layout changed");
 
 }  // namespace train

@@ -50,6 +50,11 @@ def _fbits(x: float) -> int:
     return struct.unpack("<I", struct.pack("<f", float(x)))[0]
 
 
+def _dbits(x: float) -> int:
+    """A double's bit pattern as a (signed) int64: how the ctx carries ``inv_count``."""
+    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
+
+
 def pack_ctx(fields: Dict[str, int]) -> torch.Tensor:
     """The int64 CPU ctx tensor of ``train_call``: ``fields`` (one integer per name -- a device pointer, a
     scalar or a float's bit pattern) in the order of ``torch.ops.apneauq.train_ctx_fields()``, the field list
@@ -181,7 +186,7 @@ class TrainWorkspace:
                  g_dense_w=ptr(g["output_layer/kernel"]), g_dense_b=ptr(g["output_layer/bias"]), logits=ptr(self.logits),
                  dlogit=ptr(self.dlogit), loss_sum=ptr(self.loss), B=n, n_win=n_win, groups=groups,
                  pass_base=TRAIN_PASS_BASE, window_offset=window_offset, seed=int(seed) & ((1 << 63) - 1),
-                 dropout=int(bool(dropout)), inv_count=_fbits(inv_count), inv_batch=_fbits(inv_batch),
+                 dropout=int(bool(dropout)), inv_count=_dbits(inv_count), inv_batch=_fbits(inv_batch),
                  eps=_fbits(spec.bn_epsilon), momentum=_fbits(spec.bn_momentum),
                  pass_dev=ptr(self.counters if device_counters else None), st_groups=self.groups,
                  wpart=ptr(self.wpart), det=ptr(self.det), shared0=int(self.shared0), tab=ptr(self.tab if table else None),
