@@ -28,6 +28,7 @@
 | analyze_laplace_patient_level | (new) last-layer Laplace UQ evaluation with per-window results: fits (or loads) the posterior of the Dense head, then the outputs of analyze_mcd_patient_level |
 | analyze_discrimination | (new) ROC / PR AUC and Mann-Whitney U (apnea vs normal, wrong vs right predictions) with window or patient-cluster bootstrap CIs, and the paired comparison of two detail CSVs |
 | analyze_recalibration | (new) temperature / Platt / beta recalibration of a raw prediction dump (fit set or patient cross-fit): calibration before and after on the same resamples, and the calibrated (T, N, 1) dump for the other analyze_* commands |
+| analyze_conformal | (new) split conformal prediction sets from a detail CSV: thresholds from a fit CSV and the set code of every window, or coverage / set sizes over random calibration / test splits of the patients |
 """
 from __future__ import annotations
 
@@ -614,6 +615,78 @@ def analyze_recalibration(argv=None):
             np.savez(a.state, theta=info["theta"], fold=info["fold"],
                      meta=np.array(json.dumps({"method": a.method, "objective": a.objective, "seed": a.seed,
                                                "converged": info["converged"], "n_iter": info["n_iter"]})))
+    return table
+
+
+def analyze_conformal(argv=None):
+    ap = argparse.ArgumentParser(description="Split conformal prediction sets from a per-window detail CSV: with a fit "
+                                             "CSV the thresholds are calibrated there and the set code of every input "
+                                             "window is written; without one, coverage and set sizes over random "
+                                             "calibration / test splits of the patients.")
+    ap.add_argument("--input_csv", type=str, default="./detail_patient_DE.csv",
+                    help="per-window detail CSV, read for Predicted_Probability, True_Label and Patient_ID")
+    ap.add_argument("--fit_csv", type=str, default=None, help="detail CSV of a separate calibration set (optional)")
+    ap.add_argument("--alphas", type=str, default="0.01,0.025,0.05,0.1,0.15,0.2", help="comma-separated miscoverage levels")
+    ap.add_argument("--n_splits", type=int, default=1000)
+    ap.add_argument("--cal_fraction", type=float, default=0.5)
+    ap.add_argument("--cluster", choices=["pooled", "subsample"], default="pooled")
+    ap.add_argument("--mode", choices=["class_conditional", "marginal"], default="class_conditional")
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--output_csv", type=str, default="./conformal_metrics.csv")
+    ap.add_argument("--state", type=str, default=None, help=".npz the fitted thresholds are saved to (with --fit_csv)")
+    ap.add_argument("--output_plot_dir", type=str, default="./uq_plots/conformal")
+    ap.add_argument("--no_plots", action="store_true")
+    a = ap.parse_args(argv)
+    import pandas as pd
+
+    from ..ops import conformal as conf_ops
+    from ..uq import conformal as CF
+
+    df = pd.read_csv(a.input_csv)
+    alphas = [float(v) for v in a.alphas.split(",") if v.strip()]
+    sufs = CF.level_suffixes(alphas)
+    p = df["Predicted_Probability"].to_numpy(np.float32)
+    has_y = "True_Label" in df.columns
+    for path in (a.output_csv, a.state):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    if a.fit_csv:
+        fit = pd.read_csv(a.fit_csv)
+        rows = []
+        for alpha, suf in zip(alphas, sufs):
+            cp = CF.conformal_calibrate(fit["Predicted_Probability"].to_numpy(np.float32), fit["True_Label"].to_numpy(),
+                                        alpha, a.mode)
+            sets = cp.predict_sets(p)
+            df[f"Conformal_Set{suf}"] = sets
+            if a.state:
+                stem = a.state[:-4] if a.state.endswith(".npz") else a.state
+                cp.save(stem + (suf if len(alphas) > 1 else ""))
+            row = {"alpha": alpha, "tau0": cp.tau0, "tau1": cp.tau1, "qhat": cp.qhat}
+            if has_y:
+                row.update(CF.conformal_metrics(sets, df["True_Label"].to_numpy(), valid=np.isfinite(p)))
+            rows.append(row)
+        table = pd.DataFrame(rows)
+        print(f"{a.mode}: thresholds calibrated on {len(fit)} windows of {a.fit_csv}")
+        print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
+        if a.output_csv:
+            df.to_csv(a.output_csv, index=False)
+            print(f"Saved the set codes (bit 0 = normal, bit 1 = apnea) to: {a.output_csv}")
+        return table
+    label = os.path.splitext(os.path.basename(a.input_csv))[0]
+    pids = df["Patient_ID"].to_numpy() if "Patient_ID" in df.columns else None
+    res = CF.evaluate_conformal(p, df["True_Label"].to_numpy(), label, alphas=alphas, n_splits=a.n_splits,
+                                cal_fraction=a.cal_fraction, patient_ids=pids, cluster=a.cluster, mode=a.mode,
+                                random_state=a.seed, output_dir=a.output_plot_dir, make_plots=not a.no_plots)
+    rows = [{"metric": m, "alpha": alpha, "mean": res[f"{m}{suf}"], "ci_lower": res[f"{m}{suf}_ci_lower"],
+             "ci_upper": res[f"{m}{suf}_ci_upper"]} for alpha, suf in zip(alphas, sufs) for m in conf_ops.METRICS]
+    rows += [{"metric": "coverage_violation_rate", "alpha": alpha, "mean": res[f"coverage_violation_rate{suf}"],
+              "ci_lower": np.nan, "ci_upper": np.nan} for alpha, suf in zip(alphas, sufs)]
+    table = pd.DataFrame(rows, columns=["metric", "alpha", "mean", "ci_lower", "ci_upper"])
+    print(f"{a.mode} / {a.cluster}: {a.n_splits} splits of {res['n_units']} "
+          f"{'patients' if pids is not None else 'windows'}, {res['n_valid']} valid windows")
+    print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
+    if a.output_csv:
+        table.to_csv(a.output_csv, index=False)
     return table
 
 

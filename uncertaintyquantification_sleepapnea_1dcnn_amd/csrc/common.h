@@ -66,6 +66,16 @@ __device__ __forceinline__ unsigned boot_draw(unsigned bkey, unsigned j, int n) 
   return (unsigned)(((unsigned long long)hsh * (unsigned long long)n) >> 32);
 }
 
+// Calibration / test split of conformal prediction (uq_conformal.hip; ops/rng.py split_hash is the same
+// function on tensors): a 32-bit uniform per (seed, split r, unit u).  split_key is boot_key under a salt of
+// its own, so a split never repeats a bootstrap replicate of the same seed; salt 0 decides the unit's role,
+// salt 1 (split_hash2) picks the calibrating window of a patient.
+constexpr unsigned kSplitSalt = 0x51ED270Bu, kSplitSalt2 = 0xC2B2AE35u;
+__device__ __forceinline__ unsigned split_key(unsigned seed, unsigned r, unsigned salt) {
+  return boot_key(seed ^ salt, r);
+}
+__device__ __forceinline__ unsigned split_hash(unsigned skey, unsigned u) { return mix32(skey ^ mix32(u)); }
+
 // 16-bit uniforms of channels (c, c+1), c even, at time step t.
 __device__ __forceinline__ uint32_t dropout_bits2(uint32_t skey, uint32_t t, uint32_t c_even) {
   return mix32(skey ^ ((t << 9) | (c_even >> 1)));

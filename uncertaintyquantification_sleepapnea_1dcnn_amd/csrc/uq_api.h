@@ -1,5 +1,5 @@
 // Host interface of the UQ reduction kernels (uq_reduce.hip, uq_calib.hip, uq_patient.hip, uq_rank.hip,
-// uq_laplace.hip, uq_converge.hip, uq_recal.hip), included by those files and by uq_bindings.cpp /
+// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_recal.hip), included by those files and by uq_bindings.cpp /
 // recal_bindings.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -31,6 +31,18 @@ hipError_t launch_rank_totals(const int* w, long long stride, const unsigned cha
                               int n_boot, int splits, long long* tot, hipStream_t stream);
 hipError_t launch_rank_scan(const int* w, long long stride, const unsigned char* packed, const int* bounds,
                             const long long* tot, int n, int n_boot, int splits, long long* part, hipStream_t stream);
+// uq_conformal.hip
+int conformal_tile();
+int conformal_max_segments();
+int conformal_max_alpha();
+int conformal_max_cuts();
+hipError_t launch_conformal_select(const int* unit, const unsigned char* packed, const int* within, const int* ucount,
+                                   int n_units, int n, int span, unsigned seed, int r0, int n_splits,
+                                   unsigned long long cal_thr, const int* alpha_ppm, int n_alpha, int strata, int* totals,
+                                   int* member, hipStream_t stream);
+hipError_t launch_conformal_count(const int* unit, const unsigned char* packed, const int* within, const int* ucount,
+                                  int n_units, int n, int span, unsigned seed, int r0, int n_splits,
+                                  unsigned long long cal_thr, const int* cuts, int n_cuts, int* out, hipStream_t stream);
 // uq_laplace.hip
 int laplace_max_dp();
 long long laplace_part_doubles(int D);

@@ -1,5 +1,5 @@
 // torch.library registration of the UQ reduction kernels (uq_reduce.hip, uq_calib.hip, uq_patient.hip, uq_rank.hip,
-// uq_laplace.hip, uq_converge.hip), namespace torch.ops.apneauq.
+// uq_conformal.hip, uq_laplace.hip, uq_converge.hip), namespace torch.ops.apneauq.
 #include "bind_util.h"
 #include "uq_api.h"
 
@@ -232,6 +232,103 @@ at::Tensor rank_scan(const at::Tensor& w, const at::Tensor& packed, const at::Te
   return out;
 }
 
+// Split conformal prediction (uq_conformal.hip).  The role inputs of both ops: unit (n,) int32 and packed (n,) uint8
+// over the sorted windows, and for cluster = "subsample" within (n,) int32 with ucount (P,) int32.  segments (0: the
+// most the kernel holds) caps the segments a row is cut into; the results do not depend on it.
+struct ConfInputs {
+  at::Tensor unit, packed, within, ucount;
+  const int* within_ptr = nullptr;
+  const int* ucount_ptr = nullptr;
+  int n = 0, n_units = 0, span = 1;
+};
+
+at::Tensor conf_aligned(const at::Tensor& t) {
+  auto c = t.contiguous();
+  return aligned(c, 16) ? c : c.clone();
+}
+
+ConfInputs conf_inputs(const char* op, const at::Tensor& unit, const at::Tensor& packed,
+                       const c10::optional<at::Tensor>& within, const c10::optional<at::Tensor>& ucount, int64_t r0,
+                       int64_t n_splits, int64_t cal_thr, int64_t segments) {
+  ConfInputs in;
+  TORCH_CHECK(unit.is_cuda() && unit.scalar_type() == at::kInt && unit.dim() == 1, op,
+              ": unit must be (n,) int32 on the GPU");
+  const int64_t n = unit.size(0);
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 27), op, ": n must be in 1..2^27");
+  TORCH_CHECK(packed.is_cuda() && packed.scalar_type() == at::kByte && packed.dim() == 1 && packed.size(0) == n, op,
+              ": packed must be (n,) uint8 on the GPU");
+  TORCH_CHECK(within.has_value() == ucount.has_value(), op, ": within and ucount go together");
+  TORCH_CHECK(n_splits >= 0 && r0 >= 0 && r0 + n_splits < (int64_t(1) << 31), op, ": bad split range");
+  TORCH_CHECK(cal_thr >= 0 && cal_thr <= (int64_t(1) << 32), op, ": cal_thr must be in 0..2^32");
+  TORCH_CHECK(segments >= 0 && segments <= apneauq::conformal_max_segments(), op, ": segments must be in 0..",
+              apneauq::conformal_max_segments());
+  in.unit = conf_aligned(unit);
+  in.packed = conf_aligned(packed);
+  if (within.has_value()) {
+    TORCH_CHECK(within->is_cuda() && within->scalar_type() == at::kInt && within->dim() == 1 && within->size(0) == n, op,
+                ": within must be (n,) int32 on the GPU");
+    TORCH_CHECK(ucount->is_cuda() && ucount->scalar_type() == at::kInt && ucount->dim() == 1 && ucount->size(0) >= 1 &&
+                    ucount->size(0) < (int64_t(1) << 31),
+                op, ": ucount must be (P,) int32 on the GPU");
+    in.within = conf_aligned(*within);
+    in.ucount = ucount->contiguous();
+    in.within_ptr = in.within.data_ptr<int>();
+    in.ucount_ptr = in.ucount.data_ptr<int>();
+    in.n_units = (int)in.ucount.size(0);
+  }
+  const int64_t tiles = (n + apneauq::conformal_tile() - 1) / apneauq::conformal_tile();
+  const int64_t cap = segments ? segments : apneauq::conformal_max_segments();
+  in.n = (int)n;
+  in.span = (int)((tiles + cap - 1) / cap);
+  return in;
+}
+
+// conformal_select: totals (R, 4) int32 = cal0, cal1, test0, test1 and member (R, strata, A) int32, the sorted
+// position of the calibration window of rank k(n_cal) per stratum and level (-1: k > n_cal).  Limits: A <= 32.
+std::tuple<at::Tensor, at::Tensor> conformal_select(const at::Tensor& unit, const at::Tensor& packed,
+                                                    const c10::optional<at::Tensor>& within,
+                                                    const c10::optional<at::Tensor>& ucount, int64_t seed, int64_t r0,
+                                                    int64_t n_splits, int64_t cal_thr, const at::Tensor& alpha_ppm,
+                                                    int64_t strata, int64_t segments) {
+  auto in = conf_inputs("conformal_select", unit, packed, within, ucount, r0, n_splits, cal_thr, segments);
+  TORCH_CHECK(alpha_ppm.is_cuda() && alpha_ppm.scalar_type() == at::kInt && alpha_ppm.dim() == 1 &&
+                  alpha_ppm.size(0) >= 1 && alpha_ppm.size(0) <= apneauq::conformal_max_alpha(),
+              "conformal_select: alpha_ppm must be (A,) int32 on the GPU, A in 1..32");
+  TORCH_CHECK(strata == 1 || strata == 2, "conformal_select: strata must be 1 or 2");
+  auto aa = alpha_ppm.contiguous();
+  const int64_t n_alpha = aa.size(0);
+  const at::DeviceGuard guard(in.unit.device());
+  auto totals = at::empty({n_splits, 4}, in.unit.options());
+  auto member = at::empty({n_splits, strata, n_alpha}, in.unit.options());
+  check(apneauq::launch_conformal_select(in.unit.data_ptr<int>(), in.packed.data_ptr<uint8_t>(), in.within_ptr,
+                                         in.ucount_ptr, in.n_units, in.n, in.span, (unsigned)seed, (int)r0, (int)n_splits,
+                                         (unsigned long long)cal_thr, aa.data_ptr<int>(), (int)n_alpha, (int)strata,
+                                         totals.data_ptr<int>(), member.data_ptr<int>(), cur_stream()),
+        "conformal_select");
+  return std::make_tuple(totals, member);
+}
+
+// conformal_count: (R, Q, 2) int32, the test windows of class 0 / 1 among sorted positions [0, cuts[r, q]) (cuts are
+// clamped to [0, n]).  Limits: Q <= 64.
+at::Tensor conformal_count(const at::Tensor& unit, const at::Tensor& packed, const c10::optional<at::Tensor>& within,
+                           const c10::optional<at::Tensor>& ucount, int64_t seed, int64_t r0, int64_t cal_thr,
+                           const at::Tensor& cuts, int64_t segments) {
+  TORCH_CHECK(cuts.is_cuda() && cuts.scalar_type() == at::kInt && cuts.dim() == 2 && cuts.size(1) >= 1 &&
+                  cuts.size(1) <= apneauq::conformal_max_cuts(),
+              "conformal_count: cuts must be (R, Q) int32 on the GPU, Q in 1..64");
+  const int64_t n_splits = cuts.size(0), n_cuts = cuts.size(1);
+  auto in = conf_inputs("conformal_count", unit, packed, within, ucount, r0, n_splits, cal_thr, segments);
+  auto cc = cuts.contiguous();
+  const at::DeviceGuard guard(in.unit.device());
+  auto out = at::empty({n_splits, n_cuts, 2}, in.unit.options());
+  check(apneauq::launch_conformal_count(in.unit.data_ptr<int>(), in.packed.data_ptr<uint8_t>(), in.within_ptr,
+                                        in.ucount_ptr, in.n_units, in.n, in.span, (unsigned)seed, (int)r0, (int)n_splits,
+                                        (unsigned long long)cal_thr, cc.data_ptr<int>(), (int)n_cuts, out.data_ptr<int>(),
+                                        cur_stream()),
+        "conformal_count");
+  return out;
+}
+
 // Last-layer Laplace (uq_laplace.hip).  laplace_gram: flat fp64 [(D+1)^2 H | (D+1) g | loglik | n_valid] of phi (n, D)
 // fp32, theta (D+1) fp64 and y (n) uint8.  range_len (windows per range, ops/laplace.py:range_len) fixes the order of
 // the fp64 additions; grid (0: one workgroup per range) does not change the result.  Limits: D + 1 <= 128 and the
@@ -328,6 +425,8 @@ TORCH_LIBRARY_FRAGMENT(apneauq, m) {
   m.def("patient_bootstrap(Tensor prec, Tensor? idx, int seed, int n_boot) -> Tensor");
   m.def("rank_count(Tensor pos, Tensor? idx, int seed, int b0, int n_boot, int n_sorted) -> Tensor");
   m.def("rank_scan(Tensor w, Tensor packed, Tensor bounds) -> Tensor");
+  m.def("conformal_select(Tensor unit, Tensor packed, Tensor? within, Tensor? ucount, int seed, int r0, int n_splits, int cal_thr, Tensor alpha_ppm, int strata, int segments) -> (Tensor, Tensor)");
+  m.def("conformal_count(Tensor unit, Tensor packed, Tensor? within, Tensor? ucount, int seed, int r0, int cal_thr, Tensor cuts, int segments) -> Tensor");
   m.def("laplace_gram(Tensor phi, Tensor theta, Tensor y, int range_len, int grid) -> Tensor");
   m.def("laplace_predict(Tensor phi, Tensor mx, int T) -> (Tensor, Tensor)");
   m.def("converge(Tensor probs, Tensor y, Tensor orders, Tensor counts, int rep_groups) -> Tensor");
@@ -343,6 +442,8 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("patient_bootstrap", &patient_bootstrap);
   m.impl("rank_count", &rank_count);
   m.impl("rank_scan", &rank_scan);
+  m.impl("conformal_select", &conformal_select);
+  m.impl("conformal_count", &conformal_count);
   m.impl("laplace_gram", &laplace_gram);
   m.impl("laplace_predict", &laplace_predict);
   m.impl("converge", &converge);

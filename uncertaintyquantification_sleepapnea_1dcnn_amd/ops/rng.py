@@ -102,6 +102,23 @@ def boot_row(n: int, b: int, seed: int, device) -> torch.Tensor:
     return boot_draw(seed, torch.tensor(b, device=device, dtype=torch.int64), j, n)
 
 
+SPLIT_SALT, SPLIT_SALT2 = 0x51ED270B, 0xC2B2AE35
+
+
+def split_hash(seed: int, r, u: torch.Tensor, salt: int = SPLIT_SALT) -> torch.Tensor:
+    """32-bit uniform of unit ``u`` in calibration / test split ``r`` (int64 tensors or ints, broadcast): the
+    one host definition of ``csrc/common.h`` ``split_key`` / ``split_hash``.  ``boot_key`` under a salt of its
+    own: ``SPLIT_SALT`` decides a unit's role, ``SPLIT_SALT2`` (:func:`split_hash2`) picks the calibrating
+    window of a patient."""
+    r = torch.as_tensor(r, dtype=torch.int64, device=u.device)
+    skey = _mix32_t(((seed ^ salt) & _M32) ^ _mix32_t((r * 0x9E3779B9 + 0x7F4A7C15) & _M32))
+    return _mix32_t(skey ^ _mix32_t(u))
+
+
+def split_hash2(seed: int, r, u: torch.Tensor) -> torch.Tensor:
+    return split_hash(seed, r, u, SPLIT_SALT2)
+
+
 def keep_mask_torch(key: int, samples: torch.Tensor, length: int, channels: int, rate: float) -> torch.Tensor:
     """Boolean keep-mask (len(samples), length, channels) on ``samples.device``."""
     dev = samples.device

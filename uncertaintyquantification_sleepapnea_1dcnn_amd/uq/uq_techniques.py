@@ -147,6 +147,9 @@ from .laplace import fit_laplace, laplace_predict  # noqa: E402,F401
 # post-hoc recalibration of any sampler's (T, N, 1) set: temperature / Platt / beta maps (uq/recalibration.py)
 from .recalibration import (Recalibrator, assign_folds, cross_recalibrate, evaluate_recalibration,  # noqa: E402,F401
                             fit_recalibration)
+# split conformal prediction sets from any sampler's set, and their coverage over patient splits (uq/conformal.py)
+from .conformal import (ConformalPredictor, conformal_calibrate, conformal_metrics, evaluate_conformal,  # noqa: E402,F401
+                        golden_conformal_split)
 
 
 # ===================== Uncertainty Metrics =====================
