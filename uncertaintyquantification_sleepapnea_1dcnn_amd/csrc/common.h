@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "xcd_order.h"
+
 // Bounds-checked debug builds (APNEAUQ_DEBUG=1, see build.py): device asserts on the launch
 // geometry and index invariants every kernel relies on.  Compiled out otherwise.
 #ifdef APNEAUQ_DEBUG
@@ -91,7 +93,10 @@ __device__ __forceinline__ uint32_t drop_signs2(uint32_t h, uint32_t thr2) {
   return __builtin_bit_cast(uint32_t, t) & 0x80008000u;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// Sum over the 64 lanes of a wave by xor shuffles, every lane gets it: float, double and the 64-bit
+// integer counts of the uq_* kernels (integer sums are exact; the order of a floating-point sum is fixed).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
   return v;

@@ -1,5 +1,6 @@
 // Parameter-blob layout shared by the fused whole-network kernels (fused_forward.hip: the reference
-// no-pool CNN; fused_pooled.hip: the same CNN with MaxPool1D(2) after blocks 1-5).  Both read one
+// no-pool CNN; fused_tiled.hip: the same CNN with MaxPool1D(2) after blocks 1-5 and the 30 s single-channel
+// net; fused_tiled_x3.hip: those two at fp32 precision, the fp16x3 blob below).  The bf16 kernels read one
 // model's packed parameters (ops/fused.py:pack_blob) from the same byte offsets.
 #pragma once
 #include "arch_tables.h"

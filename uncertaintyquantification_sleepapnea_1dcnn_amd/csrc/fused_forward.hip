@@ -311,11 +311,8 @@ __global__ __launch_bounds__(kThreads, 2) void fused_forward_kernel(Args A) {
     reinterpret_cast<f32x4*>(x0 + (kHalo + kR) * kX0RS)[threadIdx.x] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  // XCD-aware item assignment (T1): blocks sharing an XCD get a contiguous item range, so a
-  // Deep-Ensemble member's weights stay in one XCD's L2.  Bijective for any grid size.
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
+  // XCD-aware item assignment (xcd_order): a Deep-Ensemble member's weights stay in one XCD's L2
+  const int wg = xcd_order(blockIdx.x, gridDim.x);
   const int samples = A.n_pass * A.n_win;
   // One tile per workgroup.  (A persistent tile loop lets LICM hoist every block's address math
   // out of the loop, which blows the 256-VGPR budget; one tile per launch slot keeps it at ~206.)

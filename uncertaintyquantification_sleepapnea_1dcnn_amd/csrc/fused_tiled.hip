@@ -1,6 +1,7 @@
 // Fused whole-network inference with multi-sample tiles (gfx950 / MI355X) for the short-sequence
 // variants of the Alarcón 1D-CNN, both with the reference's filters / kernel sizes / parameter blob
-// (fused_blob.h, ops/fused.py:pack_blob):
+// (fused_blob.h, ops/fused.py:pack_blob).  Net tables, slot geometry, its compile-time checks and the
+// scaffolding shared with the fp16x3 kernel (fused_tiled_x3.hip) are in fused_tiled_geo.h.
 //
 //   * PooledNet: MaxPool1D(2, valid) after blocks 1-5 (the pooling lines commented out in
 //     /root/reference/models/train_deep_ensemble_cnns.py:36-66; the thesis' pooled `ensemble_cnn/`
@@ -15,26 +16,21 @@
 //
 //   * every weight fragment feeds 8 row tiles (blocks 1-2 of the pooled net are split into row
 //     groups of 8 tiles to bound the accumulators);
-//   * block l's input lives in LDS in per-sample slots of SIN rows: LIN valid rows, then zero rows
-//     that double as the 'same' padding of the next slot (SIN >= LIN + PAD), so the implicit-GEMM
-//     conv needs no bounds checks.  A computed GEMM row o is slot row (o / OPS) * SIN + o % OPS: all
-//     slot rows where OPS == SIN, else only the prefix a block needs (pooled blocks 4 / 5 compute the
-//     8 of 12 / 2 of 8 rows their pool keeps; the single-channel net computes 32 rows per 34-row
-//     slot, so a sample is exactly two row tiles);
-//   * taps that can never reach a valid input row are skipped: pooled block 5 (3 rows, k = 9) runs
-//     taps 3..6 for its 2 kept rows, block 6 (1 row, k = 9) only the centre tap -- a dense 256 -> 96
-//     layer, 9x fewer MFMAs than the padded conv;
+//   * block l's input lives in LDS in per-sample slots whose trailing zero rows are the next slot's 'same'
+//     padding, only the rows a block needs are computed and taps that reach no valid row are skipped
+//     (pooled block 6 is a dense 256 -> 96 layer, 9x fewer MFMAs than the padded conv): fused_tiled_geo.h;
 //   * the pooled epilogue pools before the BN clamp (exact: the clamp is monotone) on lane pairs
 //     (rows t, t^1 = lanes m, m^1, one DPP quad permute), each lane finishing two of the four
 //     channels: fold, counter-based dropout keyed by the pooled step (ops/rng.py, the masks of
 //     generic_conv.hip), bf16 store in place over the block input (barrier after the K loop; row
-//     groups write only bytes no later group reads -- static_asserts below), plus the slot's zero rows;
+//     groups write only bytes no later group reads -- geometry_ok), plus the slot's zero rows;
 //   * block 6 feeds Dense(96 -> 1) in fp32; partials are combined in a fixed order (bitwise sharding
 //     invariance).
 //   LDS per workgroup ~78 KiB -> 2 workgroups (8 waves) per CU.  Measured: profiles/pooled_fused_r3.md.
 #include "common.h"
 #include "fused_blob.h"
 #include "fused_api.h"
+#include "fused_tiled_geo.h"
 
 namespace apneauq {
 namespace tiled {
@@ -46,146 +42,36 @@ using fused::eoff;
 using fused::kDenseOff;
 using fused::KS;
 using fused::woff;
+using tgeo::Ctx;
+using tgeo::drop4;
+using tgeo::Geo;
+using tgeo::kThreads;
+using Args = tgeo::Args<__bf16>;
 
-constexpr int kThreads = 256;  // 4 waves
-
-// Per-net geometry tables.  RG / NG: row tiles per row group / row groups; WM: wave rows (4 / WM wave
-// columns over the channel tiles); NF: full channel tiles per wave; HALF: Cout tiles that do not split
-// 4 ways (224 -> 14, 96 -> 6 = 2 pairs x (2 NF + 1)) -- each wave pair shares its middle tile, one
-// wave per half of the row tiles, so every weight fragment is requested once per workgroup and all
-// waves issue the same MFMA count.  PD: k-steps of weight fragments in flight (depths 2-6 measured
-// 0.8-1.9 % slower than 1 on the pooled net: weight latency does not bound these kernels).
-struct PooledNet {
-  static constexpr int NS = 8, L = 60, CIN0 = 4;
-  static constexpr bool IM2COL = false;  // block 1 reads 2 rows x 4 channels per lane from x0
-  static constexpr int X0ROWS = 64;      // x0 slot rows per sample
-  static constexpr int LIN[6] = {60, 30, 15, 7, 3, 1};
-  static constexpr int SIN[6] = {64, 32, 16, 12, 8, 1};
-  static constexpr int OPS[6] = {64, 32, 16, 8, 2, 1};
-  static constexpr int LOUT[6] = {30, 15, 7, 3, 1, 1};  // rows stored (after the pool)
-  static constexpr bool POOL[6] = {true, true, true, true, true, false};
-  static constexpr int T0[6] = {0, 0, 0, 0, 3, 4}, T1[6] = {7, 5, 3, 7, 7, 5};
-  static constexpr int RG[6] = {8, 8, 8, 4, 1, 1}, NG[6] = {4, 2, 1, 1, 1, 1};
-  static constexpr int WM[6] = {1, 1, 1, 1, 1, 1}, NF[6] = {2, 3, 3, 1, 4, 2};
-  static constexpr bool HALF[6] = {false, false, true, true, false, false};
-  static constexpr int PD[6] = {1, 1, 1, 1, 1, 1};
-};
-
-struct Single30Net {
-  static constexpr int NS = 4, L = 30, CIN0 = 1;
-  static constexpr bool IM2COL = true;  // x0 row t holds x[t-3 .. t+4]: the 8 k of lane group h = 0
-  static constexpr int X0ROWS = 32;
-  static constexpr int LIN[6] = {30, 30, 30, 30, 30, 30};
-  static constexpr int SIN[6] = {32, 34, 34, 34, 34, 34};
-  static constexpr int OPS[6] = {32, 32, 32, 32, 32, 32};
-  static constexpr int LOUT[6] = {30, 30, 30, 30, 30, 30};
-  static constexpr bool POOL[6] = {false, false, false, false, false, false};
-  static constexpr int T0[6] = {0, 0, 0, 0, 0, 0}, T1[6] = {7, 5, 3, 7, 9, 9};
-  static constexpr int RG[6] = {8, 8, 8, 8, 8, 8}, NG[6] = {1, 1, 1, 1, 1, 1};
-  static constexpr int WM[6] = {1, 1, 1, 1, 1, 2}, NF[6] = {2, 3, 3, 1, 4, 3};
-  static constexpr bool HALF[6] = {false, false, true, true, false, false};
-  static constexpr int PD[6] = {1, 1, 1, 1, 1, 1};
-};
-
-__host__ __device__ constexpr int row_bytes(int c) { return 2 * c + 16; }  // +16 B: conflict-free rows
-constexpr int kHB = 4 * row_bytes(256);  // leading zero rows (>= PAD rows of any block)
+// LDS carve (net tables, slot geometry and its checks: fused_tiled_geo.h).  Fixed zero rows in front of
+// and behind the block inputs: 4 rows of the widest block (>= PAD rows of any block; the discarded rows'
+// taps), at least what the geometry needs.
+__host__ __device__ constexpr int row_bytes(int c) { return tgeo::Bf16Rows::row_bytes(c); }
+constexpr int kHB = 4 * row_bytes(256);
 
 template <class N>
 struct Lay {
-  static constexpr int max_act() {
-    int m = 0;
-    for (int l = 1; l < 6; ++l) m = N::NS * N::SIN[l] * row_bytes(C[l]) > m ? N::NS * N::SIN[l] * row_bytes(C[l]) : m;
-    return m;
-  }
-  static constexpr int kActBytes = kHB + max_act() + 4 * row_bytes(256);  // + trailing slack (discarded rows' taps)
-  static constexpr int kX0Lead = N::IM2COL ? 0 : 4;
-  static constexpr int kX0RowB = N::IM2COL ? 16 : N::CIN0 * 2;
-  static constexpr int kX0Bytes = (kX0Lead + N::NS * N::X0ROWS + 8) * kX0RowB;
+  static constexpr int max_act() { return tgeo::max_act<N>(); }
+  static constexpr int kActBytes = kHB + max_act() + kHB;
+  static constexpr int kX0Lead = tgeo::x0_lead<N>();
+  static constexpr int kX0RowB = tgeo::x0_row_bytes<N>();
+  static constexpr int kX0Bytes = (kX0Lead + N::NS * N::X0ROWS + tgeo::kX0Trail) * kX0RowB;
   static constexpr int kKeyBytes = 6 * N::NS * 4;
   static constexpr int kHeadBytes = 4 * N::NS * 4 + 16;
   static constexpr int kLdsBytes = kActBytes + kX0Bytes + kKeyBytes + kHeadBytes;
+  static_assert(kHB >= tgeo::lead_bytes<N>() && kHB >= tgeo::trail_bytes<N>(), "zero rows cover every tap");
   static_assert(kActBytes % 16 == 0 && kX0Bytes % 16 == 0, "LDS carve must stay 16-B aligned");
   static_assert(2 * kLdsBytes <= 160 * 1024, "two workgroups per CU");
 };
-
-template <class N, int L>
-struct Geo {
-  static constexpr int CIN = C[L], COUT = C[L + 1], K = KS[L], PAD = (KS[L] - 1) / 2;
-  static constexpr bool FIRST = L == 0, HEAD = L == 5, POOL = N::POOL[L];
-  static constexpr int NCT = COUT / 16;
-  static constexpr int CB = FIRST ? 1 : CIN / 32;
-  static constexpr int S0 = FIRST ? 0 : N::T0[L] * CB, S1 = FIRST ? 1 : N::T1[L] * CB;  // k-steps run
-  static constexpr int NWC = 4 / N::WM[L];             // wave columns
-  static constexpr int NRW = N::RG[L] / N::WM[L];      // row tiles per wave per group
-  static constexpr int SI = FIRST ? Lay<N>::kX0RowB : row_bytes(CIN);
-  static constexpr int SOUT = L < 5 ? N::SIN[L + 1] : 1, SO = row_bytes(COUT);
-  static constexpr int SPG = N::RG[L] * 16 / N::OPS[L];  // samples per row group
-};
-
-// compile-time checks of the slot geometry and the in-place hand-over
-template <class N, int L>
-constexpr bool geometry_ok() {
-  using G = Geo<N, L>;
-  const bool rowhead = N::OPS[5] == 1;
-  if (L < 5 || !rowhead) {
-    if (N::RG[L] * N::NG[L] * 16 != N::NS * N::OPS[L]) return false;  // row groups tile the computed rows
-  } else if (N::RG[L] * 16 < N::NS) {
-    return false;
-  }
-  if (N::OPS[L] > N::SIN[L] && !(L == 5 && rowhead)) return false;
-  if (G::POOL && (N::OPS[L] % 2 != 0 || 2 * N::LOUT[L] > N::OPS[L] || N::SIN[L] % 2 != 0)) return false;
-  if (L == 0 && N::OPS[L] != N::SIN[L]) return false;
-  if (L == 0 && N::SIN[L] != N::X0ROWS) return false;
-  if (N::HALF[L] ? (N::WM[L] != 1 || G::NCT != 2 * (2 * N::NF[L] + 1) || G::NRW % 2 != 0)
-                 : (G::NWC * N::NF[L] < G::NCT || N::RG[L] % N::WM[L] != 0))
-    return false;  // wave tiling covers the block
-  if (L > 0 && N::LIN[L] > 1 && N::SIN[L] < N::LIN[L] + G::PAD) return false;  // zero rows = next slot's padding
-  if (L < 5 && (N::LOUT[L] > G::SOUT || N::LOUT[L] > N::OPS[L])) return false;
-  // row group g's output ends before group g+1's first input row (minus the padding)
-  if (L >= 1 && N::NG[L] > 1 && G::SPG * G::SOUT * G::SO > (G::SPG * N::SIN[L] - G::PAD) * G::SI) return false;
-  if (L >= 1 && N::NS * N::SIN[L] * G::SI > Lay<N>::max_act()) return false;
-  // GAP head: a wave's rows are whole samples (two row tiles each)
-  if (L == 5 && !rowhead && (N::OPS[5] % 16 != 0 || N::NG[5] != 1 || N::HALF[5] || G::NRW % (N::OPS[5] / 16) != 0))
-    return false;
-  return true;
-}
-template <class N>
-constexpr bool net_ok() {
-  return geometry_ok<N, 0>() && geometry_ok<N, 1>() && geometry_ok<N, 2>() && geometry_ok<N, 3>() &&
-         geometry_ok<N, 4>() && geometry_ok<N, 5>() && C[1] % 32 == 0 && C[2] % 32 == 0 && C[3] % 32 == 0 &&
-         C[4] % 32 == 0 && C[5] % 32 == 0 && (N::IM2COL ? N::CIN0 * KS[0] <= 8 : N::CIN0 == 4);
-}
-static_assert(net_ok<PooledNet>(), "pooled geometry");
-static_assert(net_ok<Single30Net>(), "single-channel geometry");
+// the dynamic LDS size is a launch argument: pinned, so that a geometry edit cannot change it unnoticed
+static_assert(Lay<PooledNet>::kLdsBytes == 78384 && Lay<Single30Net>::kLdsBytes == 78384, "LDS bytes per workgroup");
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
-
-struct Args {
-  const __bf16* x;         // (n_win, L, CIN0) bf16, channels-last
-  const uint8_t* blob;     // (n_member, kBlobBytes) packed parameters (ops/fused.py:pack_blob)
-  float* out;              // (n_member, n_pass, n_win)
-  long long blob_stride;
-  int n_win, n_pass, n_member;
-  int tiles_per_member, total_items;
-  unsigned window_offset, pass_offset;
-  unsigned long long seed;
-  int out_logits;
-  unsigned thr[6];
-};
-
-struct Ctx {
-  const guint8* blob;
-  unsigned thr;
-};
-
-// 32-bit dropout decisions of channels (c0 .. c0+3) at step t applied to v (fp32 selects)
-__device__ __forceinline__ void drop4(f32x4& v, unsigned key, unsigned t, unsigned c0, unsigned thr) {
-  const unsigned b01 = dropout_bits2(key, t, c0), b23 = dropout_bits2(key, t, c0 + 2);
-  v[0] = (b01 & 0xFFFFu) >= thr ? v[0] : 0.f;
-  v[1] = (b01 >> 16) >= thr ? v[1] : 0.f;
-  v[2] = (b23 & 0xFFFFu) >= thr ? v[2] : 0.f;
-  v[3] = (b23 >> 16) >= thr ? v[3] : 0.f;
-}
 
 template <class N, int L, bool DROP>
 __device__ __forceinline__ void block(const Ctx X) {
@@ -251,7 +137,7 @@ __device__ __forceinline__ void block(const Ctx X) {
     const char* bbr[NRW];
 #pragma unroll
     for (int r = 0; r < NRW; ++r) {
-      const int o = rt_of(r) * 16 + m;
+      const int o = rt_of(r) * 16 + m;  // its slot row: tgeo::slot_row
       bbr[r] = act + ((o / OPSL) * SINL + o % OPSL - G::PAD) * G::SI + 16 * h;
     }
     auto step = [&](int s, const bf16x8 (&a)[NFL_A]) {
@@ -395,10 +281,12 @@ __device__ __forceinline__ void block(const Ctx X) {
     } else {
       // the zero rows LOUT .. SOUT-1 of this group's output slots (the next block's padding)
       constexpr int ZR = G::SOUT - N::LOUT[L], CPR = G::COUT / 8;  // 16-B chunks per row
-      for (int i = threadIdx.x; i < G::SPG * ZR * CPR; i += kThreads) {
-        const int sr = i / CPR, chk = i - sr * CPR;
-        const int smp = g * G::SPG + sr / ZR, tr = N::LOUT[L] + sr % ZR;
-        *reinterpret_cast<f32x4*>(act + (smp * G::SOUT + tr) * G::SO + chk * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (ZR > 0) {  // (pooled block 5 stores its one row into a one-row slot: none)
+        for (int i = threadIdx.x; i < G::SPG * ZR * CPR; i += kThreads) {
+          const int sr = i / CPR, chk = i - sr * CPR;
+          const int smp = g * G::SPG + sr / ZR, tr = N::LOUT[L] + sr % ZR;
+          *reinterpret_cast<f32x4*>(act + (smp * G::SOUT + tr) * G::SO + chk * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
       }
     }
   }
@@ -418,13 +306,10 @@ __global__ __launch_bounds__(kThreads, 2) void fused_tiled_kernel(Args A) {
     reinterpret_cast<f32x4*>(smem + Y::kActBytes - 4 * row_bytes(256))[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if (threadIdx.x < Y::kX0Lead * Y::kX0RowB / 16) reinterpret_cast<f32x4*>(x0)[threadIdx.x] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (threadIdx.x < 8 * Y::kX0RowB / 16)
+  if (threadIdx.x < tgeo::kX0Trail * Y::kX0RowB / 16)
     reinterpret_cast<f32x4*>(x0 + (Y::kX0Lead + NS * N::X0ROWS) * Y::kX0RowB)[threadIdx.x] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // XCD-aware item order (as fused_forward.hip): an XCD's workgroups take a contiguous item range
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-  const int item = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
+  const int item = xcd_order(blockIdx.x, gridDim.x);  // an XCD's workgroups take a contiguous item range
   APNEAUQ_DASSERT(item < A.total_items && blockDim.x == kThreads);
   const int member = item / A.tiles_per_member;
   const int tile = item - member * A.tiles_per_member;
@@ -461,14 +346,7 @@ __global__ __launch_bounds__(kThreads, 2) void fused_tiled_kernel(Args A) {
       reinterpret_cast<f32x4*>(x0 + (Y::kX0Lead + sl * N::X0ROWS) * Y::kX0RowB)[chk] = v;
     }
   }
-  // per-(block, sample) dropout keys: the same (seed, layer, pass, window) streams as every path
-  if (DROP && threadIdx.x < 6 * NS) {
-    const int l = threadIdx.x / NS, sl = threadIdx.x % NS;
-    const long long gs = (long long)tile * NS + sl;
-    const long long gg = gs < samples ? gs : 0;
-    const unsigned pass = (unsigned)(gg / A.n_win), win = (unsigned)(gg % A.n_win);
-    keys[threadIdx.x] = sample_key(stream_key(A.seed, (unsigned)l, A.pass_offset + pass), A.window_offset + win);
-  }
+  if constexpr (DROP) tgeo::stage_keys<N>(keys, A, tile, samples);
   __syncthreads();
 
   Ctx X;
@@ -486,58 +364,16 @@ __global__ __launch_bounds__(kThreads, 2) void fused_tiled_kernel(Args A) {
   X.thr = A.thr[5];
   block<N, 5, DROP>(X);
 
-  if (threadIdx.x < NS) {
-    const int sl = threadIdx.x;
-    const long long gs = (long long)tile * NS + sl;
-    if (gs < samples) {
-      float logit;
-      if constexpr (N::OPS[5] == 1)  // [wave][sample], L = 1: GAP is the identity
-        logit = head[sl] + head[NS + sl] + head[2 * NS + sl] + head[3 * NS + sl];
-      else {  // [sample][wave column] sums over the L rows
-        constexpr int NWC5 = 4 / N::WM[5];
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWC5; ++w) s += head[NWC5 * sl + w];
-        logit = s * (1.0f / N::L);
-      }
-      logit += reinterpret_cast<const gfloat*>(X.blob + kDenseOff)[C[6]];
-      const int pass = (int)(gs / A.n_win), win = (int)(gs % A.n_win);
-      A.out[((long long)member * A.n_pass + pass) * A.n_win + win] =
-          A.out_logits ? logit : 1.0f / (1.0f + __expf(-logit));
-    }
-  }
+  tgeo::write_logits<N>(head, reinterpret_cast<const gfloat*>(X.blob + kDenseOff), A, member, tile, samples);
 }
 
 template <class N>
 hipError_t launch(const void* x, const uint8_t* blob, long long blob_stride, float* out, int n_win, int n_pass,
                   int n_member, unsigned window_offset, unsigned pass_offset, unsigned long long seed, int dropout,
                   int out_logits, const unsigned* thr, hipStream_t stream) {
-  Args A;
-  A.x = reinterpret_cast<const __bf16*>(x);
-  A.blob = blob;
-  A.out = out;
-  A.blob_stride = blob_stride;
-  A.n_win = n_win;
-  A.n_pass = n_pass;
-  A.n_member = n_member;
-  const long long samples = (long long)n_pass * n_win;
-  const long long tiles = (samples + N::NS - 1) / N::NS;
-  if (tiles < 1 || n_member < 1) return hipSuccess;
-  if (tiles * n_member >= (1LL << 31)) return hipErrorInvalidValue;
-  A.tiles_per_member = (int)tiles;
-  A.total_items = (int)(tiles * n_member);
-  A.window_offset = window_offset;
-  A.pass_offset = pass_offset;
-  A.seed = seed;
-  A.out_logits = out_logits;
-  for (int l = 0; l < 6; ++l) A.thr[l] = thr ? thr[l] : 0u;
-  if (dropout)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_tiled_kernel<N, true>), dim3(A.total_items), dim3(kThreads),
-                       Lay<N>::kLdsBytes, stream, A);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_tiled_kernel<N, false>), dim3(A.total_items), dim3(kThreads),
-                       Lay<N>::kLdsBytes, stream, A);
-  return hipGetLastError();
+  return tgeo::launch<N>(dropout ? fused_tiled_kernel<N, true> : fused_tiled_kernel<N, false>, Lay<N>::kLdsBytes,
+                         reinterpret_cast<const __bf16*>(x), blob, blob_stride, out, n_win, n_pass, n_member,
+                         window_offset, pass_offset, seed, out_logits, thr, stream);
 }
 
 }  // namespace tiled

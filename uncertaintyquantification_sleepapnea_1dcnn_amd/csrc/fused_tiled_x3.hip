@@ -28,41 +28,27 @@
 // workgroups (8 waves) still share a CU.  Row tiles past the last sample (pooled block 5: 8 rows of one
 // 16-row tile) read finite LDS bytes and are never stored.
 #include "common.h"
+#include "f16x3.h"
 #include "fused_blob.h"
 #include "fused_api.h"
+#include "fused_tiled_geo.h"
 
 namespace apneauq {
 namespace tiled3 {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) const f16x8 gf16x8;
-
 using fused::C;
 using fused::KS;
+using tgeo::Ctx;
+using tgeo::drop4;
+using tgeo::Geo;
+using tgeo::kThreads;
+using Args = tgeo::Args<float>;
 
-constexpr int kThreads = 256;  // 4 waves
-
-__device__ __forceinline__ f32x4 mfma(const f16x8& a, const f16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// hi = fp16(a) two at a time (v_cvt_pk_f16_f32), lo = fp16(a - hi) by one v_fma_mix per element
-// (x3_layers.hip:store_chunk; bit-identical to convert / convert back / subtract / convert)
-__device__ __forceinline__ void split2(float a0, float a1, unsigned& hi, unsigned& lo) {
-  hi = __builtin_bit_cast(unsigned, (f16x2){(_Float16)a0, (_Float16)a1});
-  unsigned l;
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(hi), "v"(a0));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(hi), "v"(a1));
-  lo = l;
-}
-
-// the power of two that puts a nonzero max m into [2^13, 2^14)
-__device__ __forceinline__ int prescale_exp(float m) {
-  int e = 0;
-  if (m > 0.f && m < INFINITY) frexpf(m, &e);  // m = f 2^e, f in [0.5, 1)
-  return (m > 0.f && m < INFINITY) ? min(100, max(-100, 14 - e)) : 0;
+// The exponent of a sample whose max |v| is m: f16x3.h:prescale_exp for a finite nonzero m, and 0 (not 14)
+// for m = 0, infinity or NaN -- an all-zero sample keeps its values unscaled and a non-finite one is not
+// scaled further, which is what this kernel has always computed for them.
+__device__ __forceinline__ int sample_exp(float m) {
+  return (m > 0.f && m < INFINITY) ? prescale_exp(m) : 0;
 }
 
 // one exponent per sample of the workgroup (x0 and every block output)
@@ -83,7 +69,7 @@ __device__ __forceinline__ SA<NS> exps_from(const float* red) {
   SA<NS> o;
 #pragma unroll
   for (int j = 0; j < NS; ++j)
-    o.e[j] = prescale_exp(fmaxf(fmaxf(red[j], red[NS + j]), fmaxf(red[2 * NS + j], red[3 * NS + j])));
+    o.e[j] = sample_exp(fmaxf(fmaxf(red[j], red[NS + j]), fmaxf(red[2 * NS + j], red[3 * NS + j])));
   return o;
 }
 template <int NS>
@@ -95,73 +81,18 @@ __device__ __forceinline__ void publish_max(float (&mxs)[NS], float* red, int wa
   }
 }
 
-// Per-net geometry: as fused_tiled.hip (RG / NG row tiles per group / groups, WM wave rows, NF full
-// channel tiles per wave, HALF shared middle tiles), one row group per block.
-struct PooledNet {
-  static constexpr int NS = 4, L = 60, CIN0 = 4;
-  static constexpr bool IM2COL = false;  // block 1 reads 2 rows x 4 channels per lane (hi and lo) from x0
-  static constexpr int X0ROWS = 64;
-  static constexpr int LIN[6] = {60, 30, 15, 7, 3, 1};
-  static constexpr int SIN[6] = {64, 32, 16, 12, 8, 1};
-  static constexpr int OPS[6] = {64, 32, 16, 8, 2, 1};
-  static constexpr int LOUT[6] = {30, 15, 7, 3, 1, 1};
-  static constexpr bool POOL[6] = {true, true, true, true, true, false};
-  static constexpr int T0[6] = {0, 0, 0, 0, 3, 4}, T1[6] = {7, 5, 3, 7, 7, 5};
-  static constexpr int RG[6] = {16, 8, 4, 2, 1, 1};
-  static constexpr int WM[6] = {1, 1, 1, 1, 1, 1}, NF[6] = {2, 3, 3, 1, 4, 2};
-  static constexpr bool HALF[6] = {false, false, true, true, false, false};
-};
-
-struct Single30Net {
-  static constexpr int NS = 2, L = 30, CIN0 = 1;
-  static constexpr bool IM2COL = true;  // x0 row t holds x[t-3 .. t+4] (hi 16 B | lo 16 B)
-  static constexpr int X0ROWS = 32;
-  static constexpr int LIN[6] = {30, 30, 30, 30, 30, 30};
-  static constexpr int SIN[6] = {32, 34, 34, 34, 34, 34};
-  static constexpr int OPS[6] = {32, 32, 32, 32, 32, 32};
-  static constexpr int LOUT[6] = {30, 30, 30, 30, 30, 30};
-  static constexpr bool POOL[6] = {false, false, false, false, false, false};
-  static constexpr int T0[6] = {0, 0, 0, 0, 0, 0}, T1[6] = {7, 5, 3, 7, 9, 9};
-  static constexpr int RG[6] = {4, 4, 4, 4, 4, 4};
-  static constexpr int WM[6] = {1, 1, 1, 1, 1, 2}, NF[6] = {2, 3, 3, 1, 4, 3};
-  static constexpr bool HALF[6] = {false, false, true, true, false, false};
-};
-
-__host__ __device__ constexpr int row_bytes(int c) { return 4 * c + 16; }
-__host__ __device__ constexpr int cmax(int a, int b) { return a > b ? a : b; }
-
+// LDS carve (net tables, slot geometry and its checks: fused_tiled_geo.h): zero rows in front of the first
+// slot and behind the last exactly as far as a tap of a computed row reaches
 template <class N>
 struct Lay {
-  // slot row read by GEMM row o of block l at tap offset 0 (before - PAD)
-  static constexpr int slot_row(int l, int o) {
-    return (N::OPS[l] == N::SIN[l] || (N::OPS[5] == 1 && l == 5)) ? o : (o / N::OPS[l]) * N::SIN[l] + o % N::OPS[l];
-  }
-  static constexpr int max_act() {
-    int m = 0;
-    for (int l = 1; l < 6; ++l) m = cmax(m, N::NS * N::SIN[l] * row_bytes(C[l]));
-    return m;
-  }
-  // zero rows in front of the first slot: the taps before row 0 that a block runs
-  static constexpr int lead() {
-    int m = 0;
-    for (int l = 1; l < 6; ++l) m = cmax(m, cmax(0, (KS[l] - 1) / 2 - N::T0[l]) * row_bytes(C[l]));
-    return (m + 15) / 16 * 16;
-  }
-  // bytes past max_act() that the discarded rows of the last row tile read (finite, never stored)
-  static constexpr int trail() {
-    int m = 0;
-    for (int l = 1; l < 6; ++l) {
-      const int rows = N::RG[l] * 16;
-      const int last = slot_row(l, rows - 1) + N::T1[l] - 1 - (KS[l] - 1) / 2 + 1;
-      m = cmax(m, last * row_bytes(C[l]) - max_act());
-    }
-    return (m + 15) / 16 * 16;
-  }
+  static constexpr int max_act() { return tgeo::max_act<N>(); }
+  static constexpr int lead() { return tgeo::lead_bytes<N>(); }
+  static constexpr int trail() { return tgeo::trail_bytes<N>(); }
   static constexpr int kHB = lead();
   static constexpr int kActBytes = kHB + max_act() + trail();
-  static constexpr int kX0Lead = N::IM2COL ? 0 : 4;
-  static constexpr int kX0RowB = N::IM2COL ? 32 : 16;  // [hi | lo]
-  static constexpr int kX0Bytes = (kX0Lead + N::NS * N::X0ROWS + 8) * kX0RowB;
+  static constexpr int kX0Lead = tgeo::x0_lead<N>();
+  static constexpr int kX0RowB = tgeo::x0_row_bytes<N>();  // [hi | lo]
+  static constexpr int kX0Bytes = (kX0Lead + N::NS * N::X0ROWS + tgeo::kX0Trail) * kX0RowB;
   static constexpr int kKeyBytes = 6 * N::NS * 4;
   static constexpr int kRedBytes = 16 * N::NS;  // [4 waves][NS] maxima
   static constexpr int kHeadBytes = 4 * N::NS * 4 + 16;
@@ -169,78 +100,11 @@ struct Lay {
   static_assert(kHB % 16 == 0 && kActBytes % 16 == 0 && kX0Bytes % 16 == 0, "LDS carve must stay 16-B aligned");
   static_assert(2 * kLdsBytes <= 160 * 1024, "two workgroups per CU");
 };
-
-template <class N, int L>
-struct Geo {
-  static constexpr int CIN = C[L], COUT = C[L + 1], K = KS[L], PAD = (KS[L] - 1) / 2;
-  static constexpr bool FIRST = L == 0, HEAD = L == 5, POOL = N::POOL[L];
-  static constexpr int NCT = COUT / 16;
-  static constexpr int CB = FIRST ? 1 : CIN / 32;
-  static constexpr int S0 = FIRST ? 0 : N::T0[L] * CB, S1 = FIRST ? 1 : N::T1[L] * CB;  // k-steps run
-  static constexpr int NWC = 4 / N::WM[L];
-  static constexpr int NRW = N::RG[L] / N::WM[L];
-  static constexpr int SI = FIRST ? Lay<N>::kX0RowB : row_bytes(CIN);
-  static constexpr int SOUT = L < 5 ? N::SIN[L + 1] : 1, SO = row_bytes(COUT);
-};
-
-template <class N, int L>
-constexpr bool geometry_ok() {
-  using G = Geo<N, L>;
-  const bool rowhead = N::OPS[5] == 1;
-  const int rows = N::RG[L] * 16;
-  if (L < 5 || !rowhead) {
-    // one row group covers the computed rows (at most one partly discarded row tile)
-    if (rows < N::NS * N::OPS[L] || rows >= N::NS * N::OPS[L] + 16) return false;
-  } else if (rows < N::NS) {
-    return false;
-  }
-  if (N::OPS[L] > N::SIN[L] && !(L == 5 && rowhead)) return false;
-  if (G::POOL && (N::OPS[L] % 2 != 0 || 2 * N::LOUT[L] > N::OPS[L] || N::SIN[L] % 2 != 0)) return false;
-  if (L == 0 && (N::OPS[L] != N::SIN[L] || N::SIN[L] != N::X0ROWS)) return false;
-  if (N::HALF[L] ? (N::WM[L] != 1 || G::NCT != 2 * (2 * N::NF[L] + 1) || G::NRW % 2 != 0)
-                 : (G::NWC * N::NF[L] < G::NCT || N::RG[L] % N::WM[L] != 0))
-    return false;
-  if (L > 0 && N::LIN[L] > 1 && N::SIN[L] < N::LIN[L] + G::PAD) return false;  // zero rows = next slot's padding
-  if (L < 5 && (N::LOUT[L] > G::SOUT || N::LOUT[L] > N::OPS[L])) return false;
-  if (L == 5 && !rowhead && (N::OPS[5] % 16 != 0 || N::HALF[5] || G::NRW % (N::OPS[5] / 16) != 0)) return false;
-  return true;
-}
-template <class N>
-constexpr bool net_ok() {
-  return geometry_ok<N, 0>() && geometry_ok<N, 1>() && geometry_ok<N, 2>() && geometry_ok<N, 3>() &&
-         geometry_ok<N, 4>() && geometry_ok<N, 5>() && C[1] % 32 == 0 && C[2] % 32 == 0 && C[3] % 32 == 0 &&
-         C[4] % 32 == 0 && C[5] % 32 == 0 && (N::IM2COL ? N::CIN0 * KS[0] <= 8 : N::CIN0 == 4);
-}
-static_assert(net_ok<PooledNet>(), "pooled geometry");
-static_assert(net_ok<Single30Net>(), "single-channel geometry");
+// the dynamic LDS size is a launch argument: pinned, so that a geometry edit cannot change it unnoticed
+static_assert(Lay<PooledNet>::kLdsBytes == 75904 && Lay<Single30Net>::kLdsBytes == 79392, "LDS bytes per workgroup");
+static_assert(Lay<PooledNet>::kHB == 2736 && Lay<Single30Net>::kHB == 4160, "leading zero rows");
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
-
-struct Args {
-  const float* x;          // (n_win, L, CIN0) fp32, channels-last
-  const uint8_t* blob;     // (n_member, kBlobBytes3) packed parameters (ops/fused.py:pack_blob_x3)
-  float* out;              // (n_member, n_pass, n_win)
-  long long blob_stride;
-  int n_win, n_pass, n_member;
-  int tiles_per_member, total_items;
-  unsigned window_offset, pass_offset;
-  unsigned long long seed;
-  int out_logits;
-  unsigned thr[6];
-};
-
-struct Ctx {
-  const guint8* blob;
-  unsigned thr;
-};
-
-__device__ __forceinline__ void drop4(f32x4& v, unsigned key, unsigned t, unsigned c0, unsigned thr) {
-  const unsigned b01 = dropout_bits2(key, t, c0), b23 = dropout_bits2(key, t, c0 + 2);
-  v[0] = (b01 & 0xFFFFu) >= thr ? v[0] : 0.f;
-  v[1] = (b01 >> 16) >= thr ? v[1] : 0.f;
-  v[2] = (b23 & 0xFFFFu) >= thr ? v[2] : 0.f;
-  v[3] = (b23 >> 16) >= thr ? v[3] : 0.f;
-}
 
 // One block.  sa_in: the per-sample exponents of this block's LDS input; returns those of its output.
 template <class N, int L, bool DROP>
@@ -567,12 +431,10 @@ __global__ __launch_bounds__(kThreads, 2) void fused_tiled_x3_kernel(Args A) {
   for (int i = threadIdx.x; i < Y::trail() / 16; i += kThreads)
     reinterpret_cast<f32x4*>(smem + Y::kHB + Y::max_act())[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (threadIdx.x < Y::kX0Lead * Y::kX0RowB / 16) reinterpret_cast<f32x4*>(x0)[threadIdx.x] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (threadIdx.x < 8 * Y::kX0RowB / 16)
+  if (threadIdx.x < tgeo::kX0Trail * Y::kX0RowB / 16)
     reinterpret_cast<f32x4*>(x0 + (Y::kX0Lead + NS * N::X0ROWS) * Y::kX0RowB)[threadIdx.x] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-  const int item = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
+  const int item = xcd_order(blockIdx.x, gridDim.x);  // an XCD's workgroups take a contiguous item range
   APNEAUQ_DASSERT(item < A.total_items && blockDim.x == kThreads);
   const int member = item / A.tiles_per_member;
   const int tile = item - member * A.tiles_per_member;
@@ -606,14 +468,7 @@ __global__ __launch_bounds__(kThreads, 2) void fused_tiled_x3_kernel(Args A) {
 #pragma unroll
   for (int j = 0; j < NS; ++j) mxs[j] = xrow && sl == j ? mx : 0.f;
   publish_max<NS>(mxs, red, threadIdx.x >> 6, threadIdx.x & 63);
-  // per-(block, sample) dropout keys: the same (seed, layer, pass, window) streams as every path
-  if (DROP && threadIdx.x < 6 * NS) {
-    const int l = threadIdx.x / NS, s2 = threadIdx.x % NS;
-    const long long g2 = (long long)tile * NS + s2;
-    const long long gg = g2 < samples ? g2 : 0;
-    const unsigned pass = (unsigned)(gg / A.n_win), win = (unsigned)(gg % A.n_win);
-    keys[threadIdx.x] = sample_key(stream_key(A.seed, (unsigned)l, A.pass_offset + pass), A.window_offset + win);
-  }
+  if constexpr (DROP) tgeo::stage_keys<N>(keys, A, tile, samples);
   __syncthreads();
   const SA<NS> sa0 = exps_from<NS>(red);
   const int e0 = pick(sa0, sl);
@@ -646,58 +501,16 @@ __global__ __launch_bounds__(kThreads, 2) void fused_tiled_x3_kernel(Args A) {
   X.thr = A.thr[5];
   block<N, 5, DROP>(X, sa);
 
-  if (threadIdx.x < NS) {
-    const int s2 = threadIdx.x;
-    const long long g2 = (long long)tile * NS + s2;
-    if (g2 < samples) {
-      float logit;
-      if constexpr (N::OPS[5] == 1)
-        logit = head[s2] + head[NS + s2] + head[2 * NS + s2] + head[3 * NS + s2];
-      else {
-        constexpr int NWC5 = 4 / N::WM[5];
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWC5; ++w) s += head[NWC5 * s2 + w];
-        logit = s * (1.0f / N::L);
-      }
-      logit += reinterpret_cast<const gfloat*>(X.blob + fused::kDenseOff3)[C[6]];
-      const int pass = (int)(g2 / A.n_win), win = (int)(g2 % A.n_win);
-      A.out[((long long)member * A.n_pass + pass) * A.n_win + win] =
-          A.out_logits ? logit : 1.0f / (1.0f + __expf(-logit));
-    }
-  }
+  tgeo::write_logits<N>(head, reinterpret_cast<const gfloat*>(X.blob + fused::kDenseOff3), A, member, tile, samples);
 }
 
 template <class N>
 hipError_t launch(const float* x, const uint8_t* blob, long long blob_stride, float* out, int n_win, int n_pass,
                   int n_member, unsigned window_offset, unsigned pass_offset, unsigned long long seed, int dropout,
                   int out_logits, const unsigned* thr, hipStream_t stream) {
-  Args A;
-  A.x = x;
-  A.blob = blob;
-  A.out = out;
-  A.blob_stride = blob_stride;
-  A.n_win = n_win;
-  A.n_pass = n_pass;
-  A.n_member = n_member;
-  const long long samples = (long long)n_pass * n_win;
-  const long long tiles = (samples + N::NS - 1) / N::NS;
-  if (tiles < 1 || n_member < 1) return hipSuccess;
-  if (tiles * n_member >= (1LL << 31)) return hipErrorInvalidValue;
-  A.tiles_per_member = (int)tiles;
-  A.total_items = (int)(tiles * n_member);
-  A.window_offset = window_offset;
-  A.pass_offset = pass_offset;
-  A.seed = seed;
-  A.out_logits = out_logits;
-  for (int l = 0; l < 6; ++l) A.thr[l] = thr ? thr[l] : 0u;
-  if (dropout)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_tiled_x3_kernel<N, true>), dim3(A.total_items), dim3(kThreads),
-                       Lay<N>::kLdsBytes, stream, A);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_tiled_x3_kernel<N, false>), dim3(A.total_items), dim3(kThreads),
-                       Lay<N>::kLdsBytes, stream, A);
-  return hipGetLastError();
+  return tgeo::launch<N>(dropout ? fused_tiled_x3_kernel<N, true> : fused_tiled_x3_kernel<N, false>,
+                         Lay<N>::kLdsBytes, x, blob, blob_stride, out, n_win, n_pass, n_member, window_offset,
+                         pass_offset, seed, out_logits, thr, stream);
 }
 
 }  // namespace tiled3

@@ -81,9 +81,7 @@ __global__ __launch_bounds__(kThreads) void wgrad_kernel(WgArgs A) {
   __shared__ __attribute__((aligned(16))) char x_lds[XROWS * XRS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // XCD-aware block order: the n_ci blocks sharing a chunk range run on one XCD (shared dZ rows in L2)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xq = nwg / 8, xr = nwg % 8, xcd = bid % 8;
-  const int wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + bid / 8;
+  const int wg = xcd_order(blockIdx.x, gridDim.x);
   const int ci_t = wg % A.n_ci;
   const int co_b = (wg / A.n_ci) % A.n_co;
   const int rg = wg / (A.n_ci * A.n_co);

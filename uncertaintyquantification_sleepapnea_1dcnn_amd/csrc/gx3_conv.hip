@@ -34,16 +34,14 @@
 //     transposing ds_read_b64_tr_b16), every tap's accumulators in registers; row-group partials
 //     summed in a fixed order (deterministic).
 #include "common.h"
+#include "f16x3.h"
 #include "generic_api.h"
 
 namespace apneauq {
 
 namespace gx3 {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const f16x8 gf16x8;
 
 enum { kTrain = 1, kLinear = 2 };
 constexpr int kStatSlots = 16;
@@ -52,24 +50,16 @@ constexpr int kRowB = 160;   // LDS B row: hi 32 halfs | lo 32 halfs | 32 B pad 
 constexpr int kMaxBlocks = 48;
 constexpr int kMaxWG = 16;   // wmax_kernel workgroups per tensor
 
-__device__ __forceinline__ f32x4 mfma(const f16x8& a, const f16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// acc += A * B over one 32-deep k-step, fp16x3: small terms first
+// acc += A * B over one 32-deep k-step, fp16x3, small terms first: lo hi, hi lo, then hi hi.  (The fused
+// tiled kernel and the headline engine issue hi hi, lo hi, hi lo across several tiles instead; the order
+// rounds the accumulator differently, so it is part of what each kernel computes.)
 __device__ __forceinline__ f32x4 mfma3(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, f32x4 c) {
   c = mfma(al, bh, c);
   c = mfma(ah, bl, c);
   return mfma(ah, bh, c);
 }
 
-// exponent sa with max * 2^sa in [2^13, 2^14) (0 for an all-zero tensor)
-__device__ __forceinline__ int prescale_exp(float mx) {
-  int e = 0;
-  if (mx > 0.f && mx < INFINITY) frexpf(mx, &e);
-  return min(100, max(-100, 14 - e));
-}
-
+// plain C++ (the compiler's own convert / subtract sequence), not the asm pair of f16x3.h:split2
 __device__ __forceinline__ void split4(const f32x4& v, float sc, f16x4& hi, f16x4& lo) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -633,8 +623,8 @@ hipError_t launch_gx3_pack(int nb, const float* const* w, void* const* fwd, void
   for (int i = 0; i < nb; ++i) {
     auto& B = P.b[i];
     B.w = w[i];
-    B.fwd = reinterpret_cast<gx3::f16x8*>(fwd[i]);
-    B.dgr = reinterpret_cast<gx3::f16x8*>(dgr[i]);
+    B.fwd = reinterpret_cast<f16x8*>(fwd[i]);
+    B.dgr = reinterpret_cast<f16x8*>(dgr[i]);
     B.wsc = wsc[i];
     B.k = k[i];
     B.cin = cin[i];
@@ -667,7 +657,7 @@ hipError_t launch_gx3_conv(const float* x, long long x_rows, const void* wfrag, 
                            int mode, int in_rs, int in_off, int det_slots, hipStream_t st) {
   gx3::ConvArgs A;
   A.x = x;
-  A.wfrag = reinterpret_cast<const gx3::f16x8*>(wfrag);
+  A.wfrag = reinterpret_cast<const f16x8*>(wfrag);
   A.wsc = wsc;
   A.bias = bias;
   A.y = y;

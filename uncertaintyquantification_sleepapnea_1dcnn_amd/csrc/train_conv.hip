@@ -1379,8 +1379,10 @@ __global__ __launch_bounds__(WgCfg<l>::WAVES * 64, WgCfg<l>::MINB) void wgrad_ke
   // XCD-aware remap: hardware dispatch round-robins blockIdx over the 8 XCDs, so the nci*nco
   // workgroups of one row group (which stage the same dZ / A rows) would land on 8 different L2s
   // and each re-read the rows from HBM.  Contiguous logical ids per XCD keep a row group's blocks
-  // on one XCD, running together, so its rows come from HBM once (bijective for any grid size).
-  // (member-batched: the same remap over the XCDs the member spans)
+  // on one XCD, running together, so its rows come from HBM once.  This is xcd_order(pos.bx, gridDim.x,
+  // pos.nxcd) of xcd_order.h written out (member-batched: the same remap over the XCDs the member spans);
+  // calling the helper here swaps the operands of one scalar add in six kernels, so the text stays until
+  // these kernels change for another reason (profiles/shared_device_helpers.md).
   const int nwg = gridDim.x, bid = pos.bx, nx = pos.nxcd;
   const int xq = nwg / nx, xr = nwg % nx, xcd = bid % nx;
   const int wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + bid / nx;

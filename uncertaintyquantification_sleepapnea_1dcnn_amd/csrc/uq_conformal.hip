@@ -93,12 +93,6 @@ __device__ __forceinline__ u64 conf_pair(unsigned mask, unsigned zm) {
   return (u64)__popc(mask & ~zm) | ((u64)__popc(mask & zm) << 32);
 }
 
-__device__ __forceinline__ u64 conf_wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
 // In-place exclusive scan of seg[0, n_seg) (n_seg <= kConfMaxSeg) by the whole block; returns the total.
 __device__ __forceinline__ u64 conf_block_scan(u64* seg, int n_seg, u64* s_wave) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
@@ -157,11 +151,11 @@ __global__ __launch_bounds__(kConfThreads) void conformal_select_kernel(ConfRow 
       test_all += conf_pair(test, zm);
     }
     cal_all += cal_s;
-    const u64 v = conf_wave_sum(strata == 2 ? cal_s : (cal_s & 0xFFFFFFFFull) + (cal_s >> 32));
+    const u64 v = wave_sum(strata == 2 ? cal_s : (cal_s & 0xFFFFFFFFull) + (cal_s >> 32));
     if (lane == 0) s_seg[s] = v;
   }
-  cal_all = conf_wave_sum(cal_all);
-  test_all = conf_wave_sum(test_all);
+  cal_all = wave_sum(cal_all);
+  test_all = wave_sum(test_all);
   if (lane == 0) {
     s_tot[0][wave] = cal_all;
     s_tot[1][wave] = test_all;
@@ -258,7 +252,7 @@ __global__ __launch_bounds__(kConfThreads) void conformal_count_kernel(ConfRow a
       conf_flags<kSub>(a, k1, k2, s * seg_len + t * kConfTile + lane * kConfItems, lim, cal, test, zm);
       test_s += conf_pair(test, zm);
     }
-    const u64 v = conf_wave_sum(test_s);
+    const u64 v = wave_sum(test_s);
     if (lane == 0) s_seg[s] = v;
   }
   __syncthreads();
@@ -276,7 +270,7 @@ __global__ __launch_bounds__(kConfThreads) void conformal_count_kernel(ConfRow a
         conf_flags<kSub>(a, k1, k2, s * seg_len + t * kConfTile + lane * kConfItems, cut, cal, test, zm);
         part += conf_pair(test, zm);
       }
-      v = s_seg[s] + conf_wave_sum(part);
+      v = s_seg[s] + wave_sum(part);
     }
     if (lane == 0) {
       out[((long long)row * n_cuts + q) * 2] = (int)(unsigned)v;

@@ -32,12 +32,6 @@ __device__ __forceinline__ long long pat_q(float x) {
   return __double2ll_rn((double)c * kPatScale);
 }
 
-__device__ __forceinline__ long long pat_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
 // The running counts of passes [t0, t0 + 64) of patient cur (lane l holds pass t0 + l): one atomic per
 // (pass, patient).
 __device__ __forceinline__ void pat_flush_pass(int* __restrict__ pass_pos, int n_pat, int t_count, int t0, int cur,
@@ -52,7 +46,7 @@ __device__ __forceinline__ void pat_flush_rec(long long* __restrict__ rec, int c
   if (cur >= 0) {
 #pragma unroll
     for (int k = 0; k < kPatRec; ++k) {
-      const long long v = pat_wave_sum(a[k]);
+      const long long v = wave_sum(a[k]);
       if (lane == k && v != 0)
         atomicAdd(reinterpret_cast<unsigned long long*>(&rec[(long long)cur * kPatRec + k]), (unsigned long long)v);
     }
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(kPatThreads) void patient_bootstrap_kernel(const lo
   }
 #pragma unroll
   for (int f = 0; f < kPatFields; ++f) {
-    const long long v = pat_wave_sum(acc[f]);
+    const long long v = wave_sum(acc[f]);
     if (lane == 0) red[wave][f] = v;
   }
   __syncthreads();

@@ -84,12 +84,6 @@ __global__ __launch_bounds__(kCountThreads) void rank_count_kernel(const int* __
   }
 }
 
-__device__ __forceinline__ u64 rank_wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
 // Weights and packed bytes of sorted windows [base, base + 8), base a multiple of 4; windows outside
 // [lo, hi) come back with weight 0 and code 0.  16-B / 4-B loads where the quad lies inside the row.
 __device__ __forceinline__ void rank_load(const int* __restrict__ w_b, const unsigned char* __restrict__ packed, int base,
@@ -154,7 +148,7 @@ __global__ __launch_bounds__(kRankThreads) void rank_totals_kernel(const int* __
   }
 #pragma unroll
   for (int c = 0; c < kRankTot; ++c) {
-    const u64 v = rank_wave_sum(acc[c]);
+    const u64 v = wave_sum(acc[c]);
     if (lane == 0) red[wave][c] = v;
   }
   __syncthreads();
@@ -289,7 +283,7 @@ __global__ __launch_bounds__(kRankThreads) void rank_scan_kernel(const int* __re
   const u64 r[kRankPart] = {acc_u2, (u64)acc_groups, (u64)acc_pr, (u64)acc_ap};
 #pragma unroll
   for (int q = 0; q < kRankPart; ++q) {
-    const u64 v = rank_wave_sum(r[q]);
+    const u64 v = wave_sum(r[q]);
     if (lane == 0) s_red[wave][q] = (long long)v;
   }
   __syncthreads();

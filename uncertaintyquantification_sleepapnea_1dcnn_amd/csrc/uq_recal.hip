@@ -52,12 +52,6 @@ __device__ __forceinline__ double rc_rounded(double v) {
   return v;
 }
 
-__device__ __forceinline__ double rc_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
 // One walk of the tile's planes for NC candidates; col[c] = loss, g (3), H (6 upper) of this lane's window.
 template <int OBJ, int NC>
 __device__ __forceinline__ void rc_walk(const double* __restrict__ pl, int T, int lane, const double (&th)[NC][3],
@@ -158,16 +152,16 @@ __device__ __forceinline__ void rc_add(double* __restrict__ acc, int Q, int q, i
     m &= ~__ballot(sel);
     double mine = 0.0;
     {
-      const double v = rc_wave_sum(sel ? 1.0 : 0.0);
+      const double v = wave_sum(sel ? 1.0 : 0.0);
       if (lane == 0) mine = v;
     }
     {
-      const double v = rc_wave_sum(sel && y1 ? 1.0 : 0.0);
+      const double v = wave_sum(sel && y1 ? 1.0 : 0.0);
       if (lane == 1) mine = v;
     }
 #pragma unroll
     for (int j = 0; j < 10; ++j) {
-      const double v = rc_wave_sum(sel ? col[j] : 0.0);
+      const double v = wave_sum(sel ? col[j] : 0.0);
       if (lane == j + 2) mine = v;
     }
     // lane j is the only thread that ever touches column j of a slot this wave owns

@@ -58,16 +58,12 @@
 //     ahead), activations the B operand (LDS).  Waves tile rows x output channels (WM x WN) per layer so
 //     that each weight fragment is re-read by at most WM waves of the 256-row tile.
 #include "common.h"
+#include "f16x3.h"
 #include "x3_api.h"
 #include "x3_dense_map.h"
 
 namespace apneauq {
 namespace x3 {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) const f16x8 gf16x8;
 
 // Staging waves of a layer without loader waves: the HBM loads of the next chunk are issued by MFMA
 // waves 0..kStagers-1 only (one per SIMD), so that the partner wave keeps the matrix pipe busy while the
@@ -88,10 +84,7 @@ __host__ __device__ constexpr int row_bytes(int ck) { return 4 * ck + 32; }
 // (max R_c <= sqrt(sum R_c^2), aff_kernel): one power of two per group, folded into the affine, and no
 // per-sample tracking in the producer's epilogue (the moments are global, so this is invariant too).
 __device__ __forceinline__ int sample_prescale(unsigned rmax_bits, const float* amax) {
-  const float b = __builtin_fmaf(amax[0], __uint_as_float(rmax_bits), amax[1]);
-  int e = 0;
-  if (b > 0.f && b < INFINITY) frexpf(b, &e);  // b = m 2^e, m in [0.5, 1)
-  return min(100, max(-100, 14 - e));
+  return prescale_exp(__builtin_fmaf(amax[0], __uint_as_float(rmax_bits), amax[1]));
 }
 
 // per tile of S samples (S x 64 GEMM rows): LDS rows, chunk-buffer bytes, staged rows, 16-B staging units
@@ -123,22 +116,11 @@ __device__ __forceinline__ int opaque_tid() {
   return t;
 }
 
-__device__ __forceinline__ f32x4 mfma(const f16x8& a, const f16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 // LDS hazard barrier: orders LDS traffic only (global loads in flight stay in flight)
 __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// XCD-aware workgroup id (T1): blocks that share an XCD get a contiguous range.  Bijective.
-__device__ __forceinline__ int xcd_wg() {
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-  return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
 }
 
 // Waves: WM x WN MFMA waves, plus LW loader waves (LW > 0) that do all the input staging: HBM loads of
@@ -216,7 +198,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   const int m = lane & 15, h = lane >> 4;
   APNEAUQ_DASSERT(blockDim.x == kThreads);
 
-  const int wg = xcd_wg();
+  const int wg = xcd_order(blockIdx.x, gridDim.x);
   // tiles per group at this kernel's tile size
   const int tpg = DENSE ? (int)dense::tiles(A.n_win, kRows) : (A.n_win + S - 1) / S;
   const int total_tiles = tpg * A.groups;
@@ -421,22 +403,9 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       float a[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) a[i] = (valid && keep[i]) ? ldexpf(__builtin_fmaf(v[i], R.a[i], R.b[i]), sa) : 0.f;
-      // hi = fp16(a) two at a time (v_cvt_pk_f16_f32); lo = fp16(a - hi) in one mixed-precision FMA
-      // per element, a - hi evaluated in fp32 from hi's f16 half (op_sel_hi on src0), written straight
-      // into the pair's lo/hi half: 6 VALU per 4 elements instead of 16, bit-identical to the plain
-      // convert/convert/subtract/convert (tools/probes/split/split_check.hip, 8.4 M pairs)
-      uint2 hi, lo;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const unsigned u = __builtin_bit_cast(unsigned, (f16x2){(_Float16)a[2 * p], (_Float16)a[2 * p + 1]});
-        unsigned l;
-        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(u), "v"(a[2 * p]));
-        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                     : "+v"(l)
-                     : "v"(u), "v"(a[2 * p + 1]));
-        (p ? hi.y : hi.x) = u;
-        (p ? lo.y : lo.x) = l;
-      }
+      uint2 hi, lo;  // 6 VALU per 4 elements (f16x3.h:split2)
+      split2(a[0], a[1], hi.x, lo.x);
+      split2(a[2], a[3], hi.y, lo.y);
       char* row = buf + lrow * kRowB + 8 * q;
       *reinterpret_cast<uint2*>(row) = hi;
       *reinterpret_cast<uint2*>(row + 2 * kCK) = lo;
