@@ -4,7 +4,7 @@ BCE) on 1 x MI355X".
 The reference's training loop is Keras ``fit(batch_size=1024)`` with Adam and BCE
 (``/root/reference/models/cnn_baseline_train.py:100-102,210-217``) and the sequential Deep-Ensemble
 member loop (``/root/reference/models/train_deep_ensemble_cnns.py:125-177``).  Measured here, on the
-HIP training kernels (``ops/train_ops.py``, ``csrc/train_conv.hip``), each step a complete optimizer
+HIP training kernels (``ops/train_ops.py``, ``csrc/train_launch.hip``), each step a complete optimizer
 step (forward with batch-statistics BN and dropout, BCE, backward, Adam) of random-init weights on
 synthetic (60, 4) windows:
 

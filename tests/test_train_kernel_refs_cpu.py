@@ -274,7 +274,7 @@ def test_wgrad_allowances_catch_mistakes(l):
     a, amb = _layer_inputs(l, n)[:2]
     gw, gb, a_gw, a_gb, nw = T.wgrad64(a, dz, l, n, amb=amb)
     print(f"wgrad {l}: {nw} of {gw.numel()} entries widened")
-    rgs, rt = T.wg_rgs(l, n)
+    rgs, rt = T.wg(l, n)["rgs"], T.wg(l, n)["rt"]
     last = 2 * rt * (rgs - 1)                                                    # first sample of the last row group
     g2, b2 = T.wgrad64(a[:last], dz[:last], l, n)[:2]
     _caught(g2, gw, a_gw)                                                        # the last row group dropped

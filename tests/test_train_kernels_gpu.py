@@ -1,11 +1,11 @@
-"""Every kernel of the dedicated training path (``csrc/train_conv.hip``, ``csrc/train_reduce.hip``) launched
+"""Every kernel of the dedicated training path (``csrc/train_fwd.hip``, ``train_head.hip``, ``train_dgrad.hip``, ``train_wgrad.hip``, ``train_reduce.hip``) launched
 ALONE through ``torch.ops.apneauq.train_call`` on a ``TrainWorkspace`` whose input buffers the test fills
 itself, and held per entry to the float64 references and allowances of ``tests/train_kernel_refs.py``.
 
 The whole-step test (``test_train_gpu.py``) bounds a gradient to 12 %; a wrong halo row at one tile edge, a
 prefetched tile staged one row off, a row group counted twice or a mask drawn with the wrong layer id stay
 far below that.  Here no kernel's error leaks into the next one's test, the shapes are the smallest at which
-each dispatch path is taken (derived from the launch code's thresholds, ``train_kernel_refs``), and
+each dispatch path is taken (derived from the launch code's thresholds, read through ``train_kernel_refs.geo``), and
 ``test_train_kernel_refs_cpu.py`` shows that each allowance is at least 10 times smaller than the effect of
 such a mistake.  Each check prints its largest |err| / allowance; none may exceed 1."""
 import functools
@@ -294,7 +294,7 @@ def _head_case(ws, n, bias, dropout, seed=SEED, tag=0):
     return _dev(mag), drop.to(DEV), _dev(y)
 
 
-HEAD_N = [T.HEAD_WG * 4 + 3, T.HEAD_WG * 8 + 3]     # 2051: 2 samples per wave; 4099: 4 (over 512 workgroups each)
+HEAD_N = [2051, 4099]     # 2051: 2 samples per wave; 4099: 4 (over 512 workgroups each)
 HEAD_CASES = [(n, n, "table", 0.25, True) for n in (1, 2, 37)] + [(3, 8, "table", 0.25, True)] + \
              [(n, n, "table", 0.25, True) for n in HEAD_N] + \
              [(37, 37, m, 0.25, True) for m in ("slots", "atomic", "det")] + \
@@ -309,7 +309,8 @@ def test_head_matches_float64(n, n_alloc, mode, bias, dropout):
     backward sums of block 6.  'table': BN rows from a table the test wrote; 'slots' / 'atomic' / 'det': from
     the moment slots (rows taken from what op 5 writes for the same slots).  One sample has all 96 channels
     dropped, gamma is 0 on channel 2, a dense bias of +-30 saturates every logit with both labels present."""
-    assert T.head_spw(HEAD_N[0]) == 2 and T.head_spw(HEAD_N[1]) == 4 and all(v % (4 * T.head_spw(v)) for v in HEAD_N)
+    spw = [T.geo(v)["head"]["spw"] for v in HEAD_N]
+    assert spw == [2, 4] and all(v % (4 * k) for v, k in zip(HEAD_N, spw))
     ws = _ws(n_alloc, mode == "det")
     S = _head_prepare(ws, n, mode, bias, dropout)
     _call(S["ctx"], 1, 0, 1)
@@ -393,7 +394,7 @@ def _fwd_inputs(ws, l, n, dropout, seed=SEED, tag=0):
     return T.stage64(mag, drop, rows["s"], rows["t"], T.dsc(l - 1) if dropout else 1.0)
 
 
-FWD_BIG = [2 * T.FWD_TRAIN_GRID + 2, 2 * T.FWD_TRAIN_GRID]     # 1026: 513 tiles (prefetching persistent); 1024: plain
+FWD_BIG = [1026, 1024]     # 1026: 513 tiles (prefetching persistent); 1024: plain
 FWD_CASES = [(l, n, n, "atomic", True) for l in range(6) for n in (1, 2, 37)] + \
             [(l, 3, 8, "atomic", True) for l in range(6)] + \
             [(l, n, n, "atomic", True) for l in (1, 3) for n in FWD_BIG] + \
@@ -407,6 +408,8 @@ def test_fwd_matches_float64(l, n, n_alloc, mode, dropout):
     against ``rng.keep_mask_torch``, -0.0 on every pad and out-of-batch row, the rows beyond the last tile
     untouched, and the moment slots against the moments of the stored tile.  Channel 0 has zero weights and
     bias (kept zeros are +0.0, dropped ones -0.0), channel 1 a bias of -50."""
+    assert [T.tiles(v) - T.geo(v)["fwd_train_grid"] for v in FWD_BIG] == [1, 0]      # either side of the threshold
+    assert [[T.geo(v)["blocks"][b]["fwd"]["pf"] for b in (1, 3)] for v in FWD_BIG] == [[True, True], [False, False]]
     ws = _ws(n_alloc, mode == "det")
     S = _fwd_prepare(ws, l, n, mode, dropout)
     _call(S["ctx"], 0, l, 0)
@@ -439,8 +442,7 @@ def _fwd_check(ws, S, M=1):
     assert torch.equal(T.sign_bits(out), drop), tag + ": mask sign bits"
     assert bool((out[:, :, 0].abs() == 0).all()) and bool((out[:, :, 1].abs() == 0).all())
     _check_rows_outside(tag, R, n, SENT, NEG0)
-    pf = l in T.FWD_PF and T.tiles(n) * M > T.FWD_TRAIN_GRID and mode != "det"
-    grid = max(1, T.FWD_TRAIN_GRID // M) if pf else T.tiles(n)
+    grid = T.geo(n, M, mode == "det")["blocks"][l]["fwd"]["grid"]
     m, am = T.fwd_moments(out.abs().double(), n, grid, l)
     _hold(tag + " moment slots", ws.st[l].view(T.SLOTS, 2, -1).sum(0), m, am)
 
@@ -491,7 +493,7 @@ def _rows_of(ws, l, n, dropout, st, bst, mode, own_bwd, seed=SEED):
     return rows
 
 
-DG_BIG = 2 * T.DG_GRID + 2      # 1026: 513 tiles on 512 persistent workgroups -- one runs two tiles, the rest one
+DG_BIG = 1026      # 1026: 513 tiles on 512 persistent workgroups -- one runs two tiles, the rest one
 DG_CASES = [(l, n, n, "table", True) for l in range(1, 6) for n in (1, 2, 37)] + \
            [(l, 3, 8, "table", True) for l in range(1, 6)] + [(l, DG_BIG, DG_BIG, "table", True) for l in range(1, 6)] + \
            [(l, 37, 37, m, True) for l in (1, 4, 5) for m in ("slots", "bwd_self", "det")] + \
@@ -506,6 +508,8 @@ def test_dgrad_matches_float64(l, n, n_alloc, mode, dropout):
     'det': where the BN rows come from; 'bwd_self': the backward means summed from the slots (flag bit 0);
     'fused': the launch also reduces wgrad<l+1>'s partial region (flag bit 1; that gradient is the wgrad
     test's), its own outputs unchanged."""
+    g = T.geo(DG_BIG)           # one tile more than the persistent grid
+    assert T.tiles(DG_BIG) == g["dg_grid"] + 1 == g["blocks"][1]["dgrad"]["grid"] + 1 and g["blocks"][1]["dgrad"]["persist"]
     ws = _ws(n_alloc, mode == "det")
     S = _dgrad_prepare(ws, l, n, mode, dropout)
     _call(S["ctx"], 2, l, {"bwd_self": 1, "fused": 2}.get(mode, 0))
@@ -574,8 +578,8 @@ def test_wgrad_matches_float64(l, n, n_alloc, mode, dropout):
     launch, the partials are reduced by dgrad<l-1> (l >= 2) or by the finalize launch (l <= 1); 'atomic': no
     partials; 'slots': no table; 'bwd_self': the backward means from the slots.  n = 37 gives row-group
     counts that are no multiple of the reduction's J."""
-    assert T.wg_rgs(0, 37)[0] % T.red_J(0, 37) != 0 and T.red_J(0, 37) > 1
-    assert T.wg_rgs(4, WG_BIG[0])[1] > T.WG[4][2] >= T.wg_rgs(4, WG_BIG[1])[1]
+    assert T.wg(0, 37)["rgs"] % T.wg(0, 37)["J"] != 0 and T.wg(0, 37)["J"] > 1
+    assert T.wg(4, WG_BIG[0])["rt"] > T.wg(4, 1)["rtiles"] >= T.wg(4, WG_BIG[1])["rt"]
     ws = _ws(n_alloc)
     S = _wgrad_prepare(ws, l, n, mode, dropout)
     ctx = S["ctx"]
@@ -646,8 +650,9 @@ def test_member_batched_matches_float64(kernel, l, M, n):
     dropout seeds, every member's outputs held to ITS OWN reference (a member reading another's Args fails).
     M = 2 with even workgroup counts takes the XCD remap of ``mb_pos``, M = 3 the fallback."""
     if M == 2:   # grid.x of fwd (tiles), head (n / 4), dgrad (tiles), wgrad (blocks x row groups): all x 2 = 0 mod 8
-        grids = (T.tiles(n), n // 4, min(T.tiles(n), T.DG_GRID // M),
-                 (T.CH[5] // T.WG[5][0]) * (T.CH[6] // T.WG[5][1]) * T.wg_rgs(5, n, M)[0])
+        g = T.geo(n, M)
+        grids = (g["blocks"][3]["fwd"]["grid"], g["head"]["grid"], g["blocks"][4]["dgrad"]["grid"], g["blocks"][5]["wgrad"]["grid"])
+        assert grids[:2] == (T.tiles(n), n // 4)
         assert all((g * M) % 8 == 0 for g in grids)
     prepare, check, op, flag = {"fwd": (_fwd_prepare, _fwd_check, 0, 0), "head": (None, _head_check, 1, 1),
                                 "dgrad": (_dgrad_prepare, _dgrad_check, 2, 0),

@@ -188,7 +188,7 @@ def test_fused_input_copy_only_takes_matching_device_batches():
 
 
 def test_wgrad_partial_buffer_covers_every_smaller_batch():
-    """csrc/train_conv.hip train_wgrad_part_floats: a workspace of capacity B serves every batch n <= B
+    """csrc/train_geo.h wgrad_part_floats (train_wgrad_part_floats): a workspace of capacity B serves every batch n <= B
     (a partial last batch runs its own row grouping, which is not monotone in n: the row-tile cap changes
     at 2048 samples), so the size is the running maximum -- non-decreasing in B -- and holds the fused
     step's wgrad<0> region behind the shared one.  Host-only op: runs wherever the extension loads."""

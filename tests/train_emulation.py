@@ -1,6 +1,6 @@
 """Host emulation of the HIP training step's dataflow (same bf16 quantisation points, fp32 math).
 
-Used by the GPU tests as a tight oracle for ``csrc/train_conv.hip``: the fp32 autograd reference
+Used by the GPU tests as a tight oracle for the training kernels (``csrc/train_launch.hip``): the fp32 autograd reference
 differs from any bf16 pipeline by quantisation noise that the BatchNorm backward amplifies
 (gradients there are small residuals of large terms), so the kernels are checked against this
 emulation with tight tolerances and against autograd only for direction (cosine similarity).

@@ -1,5 +1,5 @@
-"""float64 references of the dedicated training kernels, one kernel each (``csrc/train_conv.hip``,
-``csrc/train_reduce.hip``: forward, parameter table, head, dgrad, wgrad, finalize), the per-entry allowances
+"""float64 references of the dedicated training kernels, one kernel each (``csrc/train_fwd.hip``, ``train_head.hip``,
+``train_dgrad.hip``, ``train_wgrad.hip``, ``train_reduce.hip``: forward, parameter table, head, dgrad, wgrad, finalize), the per-entry allowances
 they are compared under, and the fixtures both test files share (``test_train_kernel_refs_cpu.py`` checks
 this oracle without a GPU, ``test_train_kernels_gpu.py`` holds the kernels to it).
 
@@ -15,18 +15,26 @@ boundary is the allowance of exactly the output entries reading that element wid
 ``|w|``.  Everything is computed in torch float64 on the device of its inputs; ``rnd=False`` switches every
 internal rounding off (the composed step then equals float64 autograd, see the CPU tests).
 """
+import atexit
+import functools
+import json
 import math
+import os
+import shutil
+import subprocess
+import tempfile
 
 import numpy as np
 import torch
 
+from uncertaintyquantification_sleepapnea_1dcnn_amd.csrc import build
 from uncertaintyquantification_sleepapnea_1dcnn_amd.models.spec import DEFAULT_SPEC as SPEC
 from uncertaintyquantification_sleepapnea_1dcnn_amd.ops import rng
 
 from . import generic_kernel_refs as G
 from .generic_kernel_refs import EPS, MOMENTUM, U32, UB
 
-SR, HALO, L, SLOTS = 64, 4, 60, 16          # csrc/train_args.h kSR, kHalo, kL, kStatSlots
+SR, HALO, L, SLOTS = 64, 4, 60, 16          # csrc/train_geo.h kSR, kHalo, kL; train_args.h kStatSlots
 CH = list(SPEC.channels())                   # [4, 128, 192, 224, 96, 256, 96]
 KS = [b.kernel_size for b in SPEC.blocks]
 RATES = [b.dropout for b in SPEC.blocks]
@@ -36,48 +44,40 @@ OMM = 1.0 - MOMENTUM                         # 1.f - momentum is exact in fp32 a
 
 
 # ------------------------------------------------------------------------------------------ launch geometry
-# (read from the launch code in csrc/train_conv.hip; the batch sizes of the GPU cases are derived from these)
-FWD_TRAIN_GRID = 512        # kFwdTrainGrid: more row tiles than this -> fwd_kernel<1 / 3, MB, true>
-DG_GRID = 512               # kDgGrid: persistent dgrad workgroups (blocks with DgPF > 0)
-FWD_PF = {1, 3}             # FwdPF<l>::v > 0
-# WgCfg<l>: CIB, COB, RTILES, MINWG
-WG = [(32, 128, 2, 512), (32, 192, 8, 256), (64, 224, 8, 256), (32, 96, 16, 512), (32, 128, 16, 256),
-      (64, 96, 16, 256)]
-HEAD_WG = 512               # head_spw: up to 4 samples per wave while more than this many workgroups remain
+# Stated once, in csrc/train_geo.h.  The tests learn it by running the stand-alone host program
+# tests/train_geo_check.cpp (which also checks the header against brute force, test_train_geo_cpu.py): built
+# once per session into a temporary directory, with the wgrad table csrc/build.py would build the kernels with.
+@functools.lru_cache(maxsize=None)
+def geo_check_exe():
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    tmp = tempfile.mkdtemp(prefix="train_geo_")
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+    exe = os.path.join(tmp, "train_geo_check")
+    table = [d for d in build.EXTRA if d.startswith("-DAPNEAUQ_WG_TABLE=")]
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", f"-I{build.HERE}", *table,
+                        os.path.join(os.path.dirname(os.path.abspath(__file__)), "train_geo_check.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+@functools.lru_cache(maxsize=None)
+def geo(n, M=1, det=False):
+    """The launch geometry of M members x n samples (``--table``): ``tiles``, ``fwd_train_grid``, ``dg_grid``,
+    ``head`` (spw, grid) and per block ``fwd`` (pf, grid), ``dgrad`` (persist, grid), ``wgrad`` (cib, cob,
+    rtiles, cap, rgs, rt = row tiles per group, grid, J, ...)."""
+    r = subprocess.run([geo_check_exe(), "--table", str(n), str(M), str(int(det))], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return json.loads(r.stdout)
+
+
+def wg(l, n, M=1):
+    return geo(n, M)["blocks"][l]["wgrad"]
 
 
 def tiles(n):
     return (n + 1) // 2
-
-
-def head_spw(n, M=1):
-    spw = 1
-    while spw < 4 and n * M > HEAD_WG * 4 * spw:
-        spw *= 2
-    return spw
-
-
-def wg_rgs(l, n, M=1):
-    """Row groups of wgrad<l> (wg_rgs<l>) -> (rgs, row tiles per group)."""
-    cib, cob, rtiles, minwg = WG[l]
-    nblk = (1 if l == 0 else CH[l] // cib) * (CH[l + 1] // cob)
-    t = tiles(n)
-    cap = max(rtiles, 64) if t * M > 1024 else rtiles
-    rt = max(1, min(cap, (t * M * nblk + minwg - 1) // minwg))
-    while rt < cap and M * nblk * ((t + rt - 1) // rt) > minwg:
-        rt += 1
-    rgs = (t + rt - 1) // rt
-    return rgs, (t + rgs - 1) // rgs
-
-
-def red_J(l, n, M=1):
-    """Threads per float4 column of the partial reduction (red_job<l>)."""
-    rgs = wg_rgs(l, n, M)[0]
-    s4 = (KS[l] * CH[l] * CH[l + 1] + CH[l + 1]) // 4
-    J = 1
-    while J < 64 and rgs >= 16 * J and s4 * J < 256 * 1024:
-        J *= 2
-    return J
 
 
 # ------------------------------------------------------------------------------------------ layout
@@ -265,7 +265,7 @@ def head_chain(n, mode, M=1):
     """fp32 additions on the longest chain of one of the head's sums over samples.  'slots': the 4 spw
     samples of a workgroup (LDS atomics), then the workgroups sharing one of 16 slots (the test adds the
     slots in float64); 'atomic': every workgroup onto one address; 'det': fp64 from the per-sample records."""
-    spw = head_spw(n, M)
+    spw = geo(n, M)["head"]["spw"]
     nwg = -(-n // (4 * spw))
     return {"slots": 4 * spw + -(-nwg // SLOTS), "atomic": 4 * spw + nwg, "det": 0}[mode]
 
@@ -281,7 +281,7 @@ def head_allow(r, n, inv_batch, mode, M=1):
     za = (r["logit"].abs() - dz).clamp(min=0)
     slope = torch.sigmoid(za) * torch.sigmoid(-za)
     ch = head_chain(n, mode, M)
-    spw = head_spw(n, M)
+    spw = geo(n, M)["head"]["spw"]
     return dict(logit=dz, dlog=2.0 ** -21 * r["dlog"].abs() + inv_batch * slope * dz,
                 loss=(ch + 6) * U32 * r["loss_abs"] + (r["pmy"] * dz).sum(),
                 gw=(ch + 12 + 5 + 4) * U32 * r["gw_abs"], gb=(ch + 1) * U32 * r["gb_abs"],
@@ -350,7 +350,7 @@ def wgrad64(a, dz, l, n, M=1, amb=None, amb_dz=None):
     ap, dzp = slots_rows(a, pad), slots_rows(dz, 0)
     R = dzp.shape[0]
     gw, ab = G.wgrad64(ap, dzp, R, k, to=G.d64)
-    rgs, rt = wg_rgs(l, n, M)
+    rgs, rt = wg(l, n, M)["rgs"], wg(l, n, M)["rt"]
     chain = (128 * rt + rgs + 2) * U32
     a_gw, a_gb = chain * ab, chain * dzp.abs().sum(0)
     nw = 0

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / occupancy table of a HIP source for gfx950 (compile-only, no GPU).
 
-    python tools/kernel_resources.py uncertaintyquantification_sleepapnea_1dcnn_amd/csrc/train_conv.hip [-DFOO=1 ...]
+    python tools/kernel_resources.py uncertaintyquantification_sleepapnea_1dcnn_amd/csrc/train_wgrad.hip [-DFOO=1 ...]
 """
 import os
 import re

@@ -2,7 +2,7 @@
 // other window shapes (the "30 s single-channel" ModelSpec(30, 1)), other filter / kernel sizes.
 // Reference semantics: one Keras train_on_batch of the SURVEY §2.2 stack (cnn_baseline_train.py:55-102):
 //   z = relu(conv(h) + b);  y = BN_batch(z);  [y = MaxPool1D(2)(y)];  h' = Dropout(y)
-// The reference architecture has its own persistent, LDS-resident kernels (train_conv.hip); this
+// The reference architecture has its own persistent, LDS-resident kernels (train_fwd.hip ... train_wgrad.hip); this
 // path is built from the generic implicit-GEMM MFMA conv (generic_conv.hip, modes kTrain / kLinear)
 // plus the memory-bound pieces below, each one pass over bf16 activations:
 //

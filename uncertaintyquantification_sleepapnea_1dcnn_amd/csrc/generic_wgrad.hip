@@ -6,7 +6,7 @@
 //                 on v_mfma_f32_16x16x32_bf16.  Both operands are row-major (rows x channels) bf16
 //                 tiles staged in LDS and read with the transposing ds_read_b64_tr_b16 (K = rows);
 //                 the row order inside a 32-row k-step makes every read conflict-free on strides
-//                 that are odd multiples of 32 B (train_conv.hip tr_frag).  A workgroup owns one
+//                 that are odd multiples of 32 B (train_stage.h tr_frag).  A workgroup owns one
 //                 16-channel ci tile x 4*NCO co tiles and a contiguous range of 64-row chunks; every
 //                 tap's fragment is re-read from the same staged rows (shifted by the tap).  Few
 //                 input channels (Cin * k <= 32, the first block) use an im2col tile instead:
@@ -37,7 +37,7 @@ constexpr int kChunk = 64;  // rows staged per step (two 32-row k-steps)
 __host__ __device__ constexpr int odd32(int bytes) { return ((bytes + 31) / 32) % 2 ? (bytes + 31) / 32 * 32 : (bytes + 31) / 32 * 32 + 32; }
 
 // fragment of a 16x16x32 operand whose K index is the LDS row (32 rows from row_base), 16 columns
-// from col0: k-slot order as train_conv.hip tr_frag (conflict-free on odd-32B strides)
+// from col0: k-slot order as train_stage.h tr_frag (conflict-free on odd-32B strides)
 __device__ __forceinline__ bf16x8 tr_frag(const char* lds, int rs, int row_base, int col0) {
   const int lane = threadIdx.x & 63;
   const int h = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;

@@ -442,7 +442,7 @@ struct WgArgs {
 typedef short v4i16x __attribute__((ext_vector_type(4)));
 
 // fragment of a 16x16x32 operand whose K index is the LDS row (32 rows from row_base) and whose M/N
-// index is 16 columns from col0 (16-bit elements; the k-slot order of train_conv.hip tr_frag, the
+// index is 16 columns from col0 (16-bit elements; the k-slot order of train_stage.h tr_frag, the
 // same for both operands, conflict-free on row strides that are odd multiples of 32 B)
 __device__ __forceinline__ f16x8 tr_frag(const char* lds, int rs, int row_base, int col0) {
   const int lane = threadIdx.x & 63;

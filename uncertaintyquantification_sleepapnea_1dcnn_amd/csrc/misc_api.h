@@ -1,5 +1,5 @@
 // Host interface of the optimizer / counter / step-edge kernels (adam.hip, the counter launchers of
-// train_conv.hip), the streaming metrics (metrics.hip) and the preprocessing kernels (prep.hip), included by
+// train_launch.hip), the streaming metrics (metrics.hip) and the preprocessing kernels (prep.hip), included by
 // those files and by bindings.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -21,7 +21,7 @@ hipError_t launch_train_tail(int* counters, int ncounters, int members, const fl
                              float* const* probs, int n, hipStream_t stream);
 hipError_t launch_train_inputs(int members, const float* const* x, void* const* xd, const float* const* y,
                                float* const* yd, int n, int L, int C, int SR, hipStream_t stream);
-// train_conv.hip
+// train_launch.hip
 hipError_t train_bump_counters(int* c, int n, hipStream_t st);
 hipError_t train_stream_keys(unsigned* keys, const int* c, int n, unsigned long long seed, unsigned pass_base,
                              hipStream_t st);

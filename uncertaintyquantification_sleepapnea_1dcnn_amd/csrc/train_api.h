@@ -1,4 +1,4 @@
-// Host interface of the layer-wise training kernels (train_conv.hip), included by that file and by
+// Host interface of the layer-wise training kernels (train_launch.hip), included by that file and by
 // train_bindings.cpp.  The argument block is in train_ctx.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -1,21 +1,20 @@
-// Shared declarations of the layer-wise training kernels (train_conv.hip) and their reductions
-// (train_reduce.hip): buffer layout constants, per-layer / per-launch kernel arguments, member-batched
-// placement, BN moment helpers and the parameter table.  See train_conv.hip for the design.
+// Shared declarations of the layer-wise training kernels (train_fwd / train_head / train_dgrad /
+// train_wgrad.hip) and their reductions (train_reduce.hip): per-layer / per-launch kernel arguments,
+// member-batched placement, BN moment helpers and the parameter table.  The layout constants and the launch
+// geometry are in train_geo.h; see train_launch.hip for the design.
 #pragma once
 #include <type_traits>
 
 #include "arch_tables.h"
 #include "common.h"
 #include "train_ctx.h"
+#include "train_geo.h"
 
 namespace apneauq {
 namespace train {
 
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 
-constexpr int kL = 60, kSR = 64, kSlots = 2, kR = 128, kRT = 8, kHalo = 4, kRows = 136;
-constexpr int kRS = 256 * 2 + 32;  // LDS row stride (bytes) of the staged activation tiles
-constexpr int kThreads = 256;
 constexpr int C[7] = {4, 128, 192, 224, 96, 256, 96};  // the kernels' own objects; == arch::C / arch::KS:
 constexpr int KS[6] = {7, 5, 3, 7, 9, 9};
 constexpr bool tables_match() {
@@ -97,7 +96,6 @@ __device__ __forceinline__ int row_time(int grow) { return (grow - kHalo) & 63; 
 constexpr bool kFwdPrio = true;
 
 constexpr int kStatSlots = 16;
-constexpr int kHeadRec = 2 + 3 * 96;  // deterministic head record per sample: loss, dlogit, dW, sum dY, sum dY xhat
 // slot stride of the moment buffers: the ALLOCATED group count (a last MC-Dropout chunk may run fewer
 // groups while block 1's shared moments, written by the first chunk, keep their slots)
 __device__ __forceinline__ int st_stride(const Args& A, int Cc) { return A.st_groups * 2 * Cc; }
@@ -284,9 +282,7 @@ struct DetDst {  // up to four destination segments (consecutive column ranges; 
 __global__ void wgrad_reduce_kernel(const float* __restrict__ part, int rgs, int kcc, int cout, float* __restrict__ gw,
                                     float* __restrict__ gb, int J, TabBwd tb);
 __global__ void wgrad_reduce_mb_kernel(const Args* __restrict__ Am, int l, int rgs, int kcc, int cout, int J, int side);
-// deterministic column sums: kDetSeg row segments (pass 1, fp64 scratch [kDetSeg][w] behind the partial
-// table), then the segments in order (pass 2); w <= kDetMaxW
-constexpr int kDetSeg = 32, kDetMaxW = 512;
+// deterministic column sums (kDetSeg, kDetMaxW: train_geo.h)
 __global__ void det_pass1_kernel(const float* __restrict__ part, int n, int w, double* __restrict__ scr);
 __global__ void det_pass2_kernel(const double* __restrict__ scr, int w, DetDst d);
 __global__ void det_pass1_mb_kernel(const Args* __restrict__ Am, int n, int w, long long sbase);

@@ -1,4 +1,4 @@
-// torch.library registration of the layer-wise training kernels (train_conv.hip), namespace torch.ops.apneauq.
+// torch.library registration of the layer-wise training kernels (train_launch.hip), namespace torch.ops.apneauq.
 #include "bind_util.h"
 #include "train_api.h"
 
@@ -107,7 +107,7 @@ void train_call(const at::Tensor& ctx, int64_t op, int64_t layer, int64_t flag, 
   }
 }
 
-// Member-batched training (train_conv.hip train_launch_mb): the Args of M members' contexts in one device
+// Member-batched training (train_launch.hip train_launch_mb): the Args of M members' contexts in one device
 // array, validated to share every size / mode the launch geometry depends on.
 at::Tensor train_args_dev(const std::vector<at::Tensor>& ctxs, int64_t device) {
   const int64_t M = (int64_t)ctxs.size();

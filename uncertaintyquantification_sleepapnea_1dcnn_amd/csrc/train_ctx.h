@@ -1,4 +1,4 @@
-// The argument block of the layer-wise training kernels (train_conv.hip, train_reduce.hip): train::Layer and
+// The argument block of the layer-wise training kernels (train_fwd / train_head / train_dgrad / train_wgrad.hip, train_reduce.hip): train::Layer and
 // train::Args, passed by value to every fwd / head / dgrad / wgrad / tab launch and copied raw into the device
 // array of the member-batched step.  Seen by the kernels (through train_args.h) and by the host bindings.
 //

@@ -18,7 +18,7 @@ namespace apneauq {
 // x < rem and q otherwise (q = nwg / nx, rem = nwg % nx), and bid is the (bid / nx)-th workgroup of
 // XCD bid % nx.  A bijection of [0, nwg) for any grid size (checked for nwg <= 300 and nx = 1, 2, 4, 8
 // by tests/test_tiled_geo_cpu.py).  nx: the XCDs the grid spans (8 on MI355X; a member-batched training
-// grid spans the XCDs of one member: train_conv.hip, which keeps this expression written out).
+// grid spans the XCDs of one member: train_wgrad.hip, which keeps this expression written out).
 __host__ __device__ __forceinline__ constexpr int xcd_order(int bid, int nwg, int nx = 8) {
   const int q = nwg / nx, rem = nwg % nx, xcd = bid % nx;
   return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / nx;

@@ -1,4 +1,4 @@
-"""Host orchestration of the layer-wise HIP training kernels (``csrc/train_conv.hip``).
+"""Host orchestration of the layer-wise HIP training kernels (``csrc/train_launch.hip`` and the ``train_*.hip`` kernel files).
 
 One optimizer step (Keras semantics) is ~22 launches on one stream:
 
@@ -31,7 +31,7 @@ from . import _ext, fused, rng
 
 SR, HALO, ROWS_PER_TILE = 64, 4, 128
 TRAIN_PASS_BASE = 1 << 30
-STAT_SLOTS = 16  # must equal kStatSlots in csrc/train_conv.hip
+STAT_SLOTS = 16  # must equal kStatSlots in csrc/train_args.h
 
 
 def supports(spec: ModelSpec) -> bool:
@@ -100,7 +100,7 @@ class TrainWorkspace:
         bf = torch.bfloat16
         self.x = torch.zeros(rows0, ch[0], dtype=bf, device=dev)
         # -0.0 everywhere: the halo rows before the first / after the last tile and the 4 pad rows of
-        # every sample are never written by the kernels (train_conv.hip copy-out of the valid rows), and -0.0
+        # every sample are never written by the kernels (train_fwd.hip copy-out of the valid rows), and -0.0
         # decodes to A = 0 (decode_pair) like a dropped element
         self.R = [torch.empty(rows0 if l == 0 else rows, ch[l + 1], dtype=bf, device=dev).fill_(-0.0)
                   for l in range(6)]
@@ -110,7 +110,7 @@ class TrainWorkspace:
         self.dZ = [torch.zeros(rows, ch[l + 1], dtype=bf, device=dev) if (with_backward and l >= 1)
                    else torch.zeros(16, dtype=bf, device=dev) for l in range(6)]
         # BN moment sums: STAT_SLOTS interleaved copies per layer (kernels add into slot wg % S and
-        # readers sum the slots; train_conv.hip kStatSlots) -> st[S][groups][2][C], bst[S][2][C] (fp64)
+        # readers sum the slots; train_args.h kStatSlots) -> st[S][groups][2][C], bst[S][2][C] (fp64)
         S = STAT_SLOTS
         self.st_all = torch.zeros(sum(S * self.groups * 2 * ch[l + 1] for l in range(6)), dtype=torch.float64,
                                   device=dev)
@@ -138,9 +138,9 @@ class TrainWorkspace:
         self.deterministic = bool(deterministic) and with_backward and self.groups == 1 and not self.shared0
         self.det = (torch.empty(int(_ext.ops().train_det_size(self.B)), device=dev) if self.deterministic else None)
         # single-device training: per-layer BN parameter table, written once per step after the
-        # forward kernels (train_conv.hip Args::tab / tab_kernel)
+        # forward kernels (train_ctx.h Args::tab / tab_kernel)
         self.tab = torch.zeros(6 * 6 * 256, device=dev) if with_backward else None
-        # training head: slotted dense-weight / loss / dense-bias sums (train_conv.hip Args::hpart)
+        # training head: slotted dense-weight / loss / dense-bias sums (train_ctx.h Args::hpart)
         self.hpart = torch.zeros(STAT_SLOTS * (ch[6] + 2), device=dev) if with_backward else None
         self.y = torch.zeros(self.B, device=dev)
         self.logits = torch.zeros(self.B, device=dev)
@@ -197,7 +197,7 @@ class TrainWorkspace:
 
     def pack(self) -> None:
         """bf16 MFMA fragments of all six conv kernels (forward + dgrad orientation) in ONE launch
-        (csrc/generic_wgrad.hip pack_kernel: the same fragment layout as train_conv.hip's per-layer
+        (csrc/generic_wgrad.hip pack_kernel: the same fragment layout as the training kernels' per-layer
         pack for channel counts that are multiples of 16; block 1 has no dgrad)."""
         v = self.model.store.views
         if not hasattr(self, "_no_dgr"):
@@ -250,7 +250,7 @@ DETERMINISTIC = os.environ.get("APNEAUQ_DETERMINISTIC", "0") not in ("", "0")
 OVERLAP = os.environ.get("APNEAUQ_TRAIN_OVERLAP", "0") not in ("", "0")
 # Fused reductions (single-device atomic-mode steps): wgrad_l's partial sums are reduced by the workgroups
 # of dgrad_{l-1} as they finish their tiles, those of wgrad_1 / wgrad_0 by one launch with the BN finalize
-# -- 7 reduce / finalize launches become 1 (csrc/train_conv.hip train_launch_dgrad / _finalize; the same
+# -- 7 reduce / finalize launches become 1 (csrc/train_launch.hip train_launch_dgrad / _finalize; the same
 # column split and summation order, so the gradients equal the separate reduces' bitwise).  Up to
 # FUSED_MAX_BATCH samples: dgrad's 8 waves per CU run the reduction latency-bound, ~2x the reduce
 # launch's time, which only the launch overhead saved at small batches pays for (batch 1024: -13 us of
@@ -501,7 +501,7 @@ class GraphedEnsembleStep:
     """One optimizer step of M ensemble members (same architecture and batch size, one GPU) as ONE
     captured HIP graph whose layer kernels are member-batched: every forward / head / dgrad / wgrad /
     finalize launch covers all members (``gridDim.z = M``, each member's pointers from a device array
-    of kernel arguments, ``csrc/train_conv.hip:train_launch_mb``).  A batch-1024 step of this CNN is
+    of kernel arguments, ``csrc/train_launch.hip:train_launch_mb``).  A batch-1024 step of this CNN is
     ~500 workgroups per launch -- one round on 256 CUs with its memory phases exposed back to back --
     so stacking the members in one launch fills the machine instead of overlapping them on streams
     (``training/trainer.py:fit_concurrent``).  Per member the step is exactly
