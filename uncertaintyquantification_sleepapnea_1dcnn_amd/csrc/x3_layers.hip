@@ -47,6 +47,12 @@
 //     holds it); only the grouping of the fp32 per-tile moment partials differs.  Index map:
 //     x3_dense_map.h; measurements: profiles/x3_dense_rows.md.  Block 6 (per-sample masked sums) and the
 //     per-sample-prescale variants (bitwise chunk invariance, whole-slot prescale) keep slots;
+//   * the epilogue runs on every MFMA wave of the workgroup at once (the matrix pipe idles meanwhile), so the
+//     dense-row kernels keep it short: every channel tile's bias is loaded and waited for ahead of the first
+//     store, so that no memory wait stands between the stores of a tile (they used to be acknowledged one
+//     by one), and where a layer's loader waves have the slack (block 5, mask_tab_layer) they draw the output
+//     mask during the main loop into an LDS bit table that the epilogue only applies to the sign bit
+//     (profiles/x3_epilogue_offload.md);
 //   * the input channels stream through LDS in chunks of 32, double-buffered: while the MFMA waves
 //     consume chunk c, the loader waves write chunk c+1 (BN affine + dropout + fp16 split of registers
 //     loaded one chunk earlier) and issue the HBM loads of chunk c+2; one LDS-only barrier per chunk,
@@ -97,9 +103,19 @@ __host__ __device__ constexpr int buf_bytes(int S, int ck) { return lds_rows(S) 
 // the two most recently staged tiles (written by the staging waves): [2][64 S] output-mask words of the
 // tile's rows, [2][tab_rows] descriptor and input-mask word of every staged row
 __host__ __device__ constexpr int tab_rows(int S, int ks) { return kSR * S + (ks - 1); }  // the tile's rows + 2 PAD
-__host__ __device__ constexpr int lds_bytes(int S, int cout, int ck, int ks, bool dense_rows = false) {
+// and, where a dense-row layer has loader waves (mask_tab), the output keep-bits of the current tile, drawn by
+// them: [64 S rows][cout / 16] 16-bit words, bit c % 16 of word c / 16 = keep (row, channel c)
+__host__ __device__ constexpr int mask_tab_bytes(int S, int cout) { return kSR * S * (cout / 16) * 2; }
+// The layers that do so: a dense-row kernel with loader waves where it measured faster, which is block 5
+// (96 -> 256, k 9: +1 %).  Block 3 (192 -> 224, k 3: 18 k-steps per tile and the most VALU per MFMA of all
+// layers) lost 0.5 - 2.4 % with the same draw on its loader waves, and block 4's mask stays with its consumer
+// (profiles/x3_epilogue_offload.md); the code below is written for any of them.
+__host__ __device__ constexpr bool mask_tab_layer(int cin, int cout, int ks, int lw, bool dense_rows) {
+  return dense_rows && lw > 0 && cin == 96 && cout == 256 && ks == 9;
+}
+__host__ __device__ constexpr int lds_bytes(int S, int cout, int ck, int ks, bool dense_rows = false, bool mask_tab = false) {
   return 2 * (dense_rows ? dense::lds_rows(kSR * S) * row_bytes(ck) : buf_bytes(S, ck)) + 2 * cout * 8 + 2 * S * 4 +
-         (dense_rows ? 2 * kSR * S * 4 + 2 * tab_rows(S, ks) * 8 : 0);
+         (dense_rows ? 2 * kSR * S * 4 + 2 * tab_rows(S, ks) * 8 : 0) + (dense_rows && mask_tab ? mask_tab_bytes(S, cout) : 0);
 }
 
 // global-address-space load (keeps global_load_*, never flat_*)
@@ -180,7 +196,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   // about a row depends on (tile, row) only, not on the chunk or the channel tile, so the staging waves
   // compute it once per tile, one thread per row, and every chunk and channel tile looks it up:
   //   stab[tile & 1][staged row]  descriptor (LDS row, step, window slot, valid), input-mask word key ^ (t << 9)
-  //   ektab[tile & 1][tile row]   output-mask word where the epilogue draws the block's mask
+  //   ektab[tile & 1][tile row]   output-mask word where the layer draws the block's mask (read by the epilogue,
+  //                               or by the loader waves that draw it for the epilogue: mtab below)
   // A tile's tables are written with the last chunk of the tile before it (the first tile's before the
   // first barrier): one chunk barrier ahead of their first reader, the staging of the tile's chunk 0, and
   // a whole tile after the last reader of the tables they replace (tile - 2, the parity).  The slot
@@ -190,6 +207,25 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   static_assert(!DENSE || CIN / CK >= 2, "row tables: a tile's tables are written one chunk of the same workgroup ahead");
   unsigned* ektab = reinterpret_cast<unsigned*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4);
   uint2* stab = reinterpret_cast<uint2*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4 + 2 * kRows * 4);
+  // Output keep-bits of the current tile (mask_tab_layer).  Where the epilogue
+  // stores the block's mask in the sign bit (A.sign_out), the loader waves draw it during the tile's main
+  // loop, from the same ektab mask words and the same hash, and the epilogue only inserts the bits: no hash
+  // and no threshold compare on an MFMA wave.  mtab[row][COUT / 16]: bit c % 16 of word c / 16 keeps channel
+  // c, so the 16-bit word of an accumulator tile's row holds the lane's four bits at 4 h.  kMtT loader
+  // threads share a row, kMtW words each, kMtPhase of them per chunk iteration.
+  // One table, no parity, no barrier of its own.  Tile T's epilogue runs in the MFMA waves' iteration of its
+  // chunk NCH - 1, between the chunk barriers of iterations NCH - 2 and NCH - 1; the loaders write T's bits in
+  // their iterations of chunks 0 .. NCH - 2, so the last write is before the barrier ahead of the epilogue and
+  // the first one after the barrier behind the epilogue of tile T - 1 (a group change only adds barriers, on
+  // both sides alike).  That takes one iteration at least: NCH >= 2.  The ektab row read here was written one
+  // barrier or more earlier, and its parity is rewritten (tile T + 2) in iteration NCH - 2 of tile T + 1.
+  constexpr bool kMaskTab = mask_tab_layer(CIN, COUT, KS, LW, DENSE);
+  constexpr bool kBiasHoist = DENSE;  // the epilogue loads every channel tile's bias ahead of its first store
+  constexpr int kMtRowW = COUT / 16, kMtT = kMaskTab ? kST / kRows : 1, kMtW = kMtRowW / kMtT;
+  constexpr int kMtPhase = (kMtW + (NCH > 1 ? NCH - 2 : 0)) / (NCH > 1 ? NCH - 1 : 1);
+  static_assert(!kMaskTab || NCH >= 2, "mask table: written in the chunk iterations ahead of the tile's last");
+  static_assert(!kMaskTab || (kST % kRows == 0 && kMtRowW % kMtT == 0), "mask table: whole words per loader thread");
+  unsigned short* mtab = reinterpret_cast<unsigned short*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4 + 2 * kRows * 4 + 2 * kTabRows * 8);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -275,6 +311,30 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
           const int t = dense::desc_step(d);
           stab[(tile & 1) * kTabRows + i] = uint2{d, hash_in ? dense::mask_word(sample_key(ikey, win), t) : 0u};
           if (mask_out && rel >= 0 && rel < kRows) ektab[(tile & 1) * kRows + rel] = dense::mask_word(sample_key(okey, win), t);
+        }
+      }
+    }
+  };
+  // loader waves, iteration of chunk c < NCH - 1 of the tile: words c kMtPhase .. of the thread's kMtW words
+  // of the tile's keep-bit table; bits 2 p, 2 p + 1 of a word are the two halves of mix32(kt ^ (8 word + p)),
+  // the epilogue's dropout_bits2(key, t, 16 word + 2 p)
+  auto draw_mask = [&](int tile, int c) {
+    if constexpr (kMaskTab) {
+      const int tid = opaque_tid() - kSBase, row = tid / kMtT, w0 = (tid % kMtT) * kMtW;
+      const unsigned kt = ektab[(tile & 1) * kRows + row];
+      unsigned short* dst = mtab + row * kMtRowW + w0;
+#pragma unroll
+      for (int j = 0; j < kMtPhase; ++j) {
+        const int i = c * kMtPhase + j;
+        if (i < kMtW) {
+          const unsigned cp = (unsigned)(w0 + i) * 8u;
+          unsigned bits = 0u;
+#pragma unroll
+          for (int p = 0; p < 8; ++p) {
+            const unsigned b = mix32(kt ^ (cp + p));
+            bits |= ((b & 0xFFFFu) >= A.thr_out ? 1u : 0u) << (2 * p) | ((b >> 16) >= A.thr_out ? 1u : 0u) << (2 * p + 1);
+          }
+          dst[i] = (unsigned short)bits;
         }
       }
     }
@@ -541,11 +601,29 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     }
     const long long left = (long long)A.n_win * kL - w0;
     const int rows_left = DENSE ? (int)(left < kRows ? left : kRows) : 0;
+    // dense rows: the bias of every channel tile is loaded, and waited for, ahead of the first store.  The
+    // stores of a row tile sit behind the lanes' `valid` branch, and the memory counter is one in-order count
+    // of loads and stores: with the bias load still pending on the path that skips a branch, every later row
+    // tile waited for the whole counter, that is for the previous row tile's store to be acknowledged, 16
+    // write round trips in a row per tile and wave while the matrix pipe stood idle
+    // (profiles/x3_epilogue_offload.md).  Once nothing loaded is pending, the stores drain behind the
+    // epilogue's arithmetic and the next tile's first k-step.
+    f32x4 bq[kBiasHoist ? NCT : 1];
+    if constexpr (kBiasHoist) {
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) bq[ct] = gld<f32x4>(bias + (ct0 + ct) * 16 + 4 * h);
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) asm volatile("" : "+v"(bq[ct]));  // the wait lands here, once
+    }
     // channel-tile outer: only one tile's 4 channels of sums are live at a time
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
       const int co0 = (ct0 + ct) * 16 + 4 * h;
-      const f32x4 b4 = gld<f32x4>(bias + co0);
+      f32x4 b4;
+      if constexpr (kBiasHoist)
+        b4 = bq[ct];
+      else
+        b4 = gld<f32x4>(bias + co0);
       f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1, k1 = s1, k0 = s1;
       // dense rows: row, address and mask word of the lane's row tiles are re-derived per channel tile (an
       // add or an LDS read each) instead of being kept in NRT registers beside the accumulators
@@ -553,6 +631,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       if constexpr (DENSE) asm volatile("" : "+v"(mo));
       const int rel0 = rt0 * 16 + mo;  // the lane's row of the wave's first row tile
       const unsigned* ek = ektab + (tile & 1) * kRows + rel0;
+      const unsigned short* mt = mtab + rel0 * kMtRowW + (ct0 + ct);  // kMaskTab: the keep bits of the lane's rows
       float* orow = DENSE ? A.out + (((long long)g * A.n_win * kL + w0 + rel0) * COUT + co0) : nullptr;
 #pragma unroll
       for (int rt = 0; rt < NRT; ++rt) {
@@ -569,7 +648,10 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
         for (int e = 0; e < 4; ++e) r[e] = fmaxf(__builtin_fmaf(acc[ct][rt][e], wsq[rt >> 2], b4[e]), 0.f);
         acc[ct][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
         bool keep[4] = {true, true, true, true};
-        if (drop) {
+        unsigned sgn = 0u;  // kMaskTab: the complement of the lane's four keep bits (bits 0..3)
+        if constexpr (kMaskTab) {
+          if (drop) sgn = ~((unsigned)mt[rt * 16 * kMtRowW] >> (4 * h));
+        } else if (drop) {
           // the row's mask word: dropout_bits2(key, t, co0) and (key, t, co0 + 2) are one xor and mix32 each
           unsigned b01, b23;
           if constexpr (DENSE) {
@@ -597,7 +679,10 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
           if constexpr (!LAST) {
             const long long sample = (long long)g * A.n_win + w;
             f32x4 o = r;
-            if (drop) {  // the mask travels in the sign bit (-0 for a dropped zero)
+            if constexpr (kMaskTab) {  // a dropped element takes the sign bit, a kept one stays as it is
+#pragma unroll
+              for (int e = 0; e < 4; ++e) o[e] = __uint_as_float(__float_as_uint(r[e]) | ((sgn << (31 - e)) & 0x80000000u));
+            } else if (drop) {  // the mask travels in the sign bit (-0 for a dropped zero)
 #pragma unroll
               for (int e = 0; e < 4; ++e) o[e] = keep[e] ? r[e] : __builtin_copysignf(r[e], -1.f);
             }
@@ -697,6 +782,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
         }
         // chunk it+1 into the buffer compute(it-1) read (every wave passed the barrier after it)
         if (stager && it + 1 < total) store_chunk(chunk_tile(it + 1), (it + 1) % NCH, smem + ((it + 1) & 1) * kBufB, s0);
+        // this tile's output keep-bits, a share per iteration ahead of its last (kMaskTab)
+        if (kMaskTab && stager && mask_out && c < NCH - 1) draw_mask(tile, c);
         lds_barrier();
         if (stager && it + 2 < total) load_chunk(chunk_tile(it + 2), (it + 2) % NCH, s0);
       }
@@ -938,7 +1025,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs A) {
 // ------------------------------------------------------------------------------- launch helpers
 template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS, bool DENSE = false>
 hipError_t launch_layer(const LayerArgs& A, int grid, hipStream_t stream) {
-  constexpr int lds = lds_bytes(S, COUT, CK, KS, DENSE);
+  constexpr int lds = lds_bytes(S, COUT, CK, KS, DENSE, mask_tab_layer(CIN, COUT, KS, LW, DENSE));
   static_assert(WPC * lds <= 160 * 1024, "LDS of the workgroups sharing a CU");
   auto k = layer_kernel<CIN, COUT, KS, S, WM, WN, LAST, LW, CK, WPC, PS, DENSE>;
   static bool attr = false;
