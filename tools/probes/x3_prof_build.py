@@ -28,13 +28,13 @@ extern "C" void x3_prof_reset() {
 namespace apneauq {
 namespace x3 {
 """)
-    s = rep(s, """      compute_chunk(c, smem + (it & 1) * kBufB, wcur, wnxt, []() {});
+    s = rep(s, """      compute_chunk(c, tile_off(tile), smem + (it & 1) * kBufB, wcur, wnxt, []() {});
       if (c == NCH - 1) epilogue(tile);
       lds_barrier();
     }
     flush_stats(g_cur);
     return;""", """      unsigned long long q0 = PSTAMP();
-      compute_chunk(c, smem + (it & 1) * kBufB, wcur, wnxt, []() {});
+      compute_chunk(c, tile_off(tile), smem + (it & 1) * kBufB, wcur, wnxt, []() {});
       unsigned long long q1 = PSTAMP();
       if (c == NCH - 1) epilogue(tile);
       unsigned long long q2 = PSTAMP();
@@ -57,12 +57,15 @@ namespace x3 {
 #pragma unroll 1
     for (int it = 0; it < total; ++it) {""")
     s = rep(s, """        if (stager && it + 1 < total) store_chunk(chunk_tile(it + 1), (it + 1) % NCH, smem + ((it + 1) & 1) * kBufB, s0);
+        // this tile's output keep-bits, a share per iteration ahead of its last (kMaskTab)
+        if (kMaskTab && stager && mask_out && c < NCH - 1) draw_mask(tile, c);
         lds_barrier();
         if (stager && it + 2 < total) load_chunk(chunk_tile(it + 2), (it + 2) % NCH, s0);
       }
       flush_stats(g_cur);
       return;""", """        unsigned long long q0 = PSTAMP();
         if (stager && it + 1 < total) store_chunk(chunk_tile(it + 1), (it + 1) % NCH, smem + ((it + 1) & 1) * kBufB, s0);
+        if (kMaskTab && stager && mask_out && c < NCH - 1) draw_mask(tile, c);
         unsigned long long q1 = PSTAMP();
         lds_barrier();
         unsigned long long q2 = PSTAMP();
@@ -84,7 +87,7 @@ namespace x3 {
       if (stager && total > 1) load_chunk(chunk_tile(1), 1 % NCH, s0);
 #pragma unroll 1
       for (int it = 0; it < total; ++it) {""")
-    s = rep(s, """    compute_chunk(c, buf, wcur, wnxt, [&]() {
+    s = rep(s, """    compute_chunk(c, tile_off(tile), buf, wcur, wnxt, [&]() {
       if (stager && it + 1 < total) store_chunk(chunk_tile(it + 1), (it + 1) % NCH, nbuf, s0);
     });
     if (c == NCH - 1) epilogue(tile);
@@ -93,7 +96,7 @@ namespace x3 {
   }
   flush_stats(g_cur);
 }""", """    unsigned long long q0 = PSTAMP();
-    compute_chunk(c, buf, wcur, wnxt, [&]() {
+    compute_chunk(c, tile_off(tile), buf, wcur, wnxt, [&]() {
       if (stager && it + 1 < total) store_chunk(chunk_tile(it + 1), (it + 1) % NCH, nbuf, s0);
     });
     unsigned long long q1 = PSTAMP();
@@ -126,8 +129,8 @@ namespace x3 {
   if (stager && total > 1) load_chunk(chunk_tile(1), 1 % NCH, s0);
   load_a(wbase(t_begin), ah, al);""")
     if "nohash" in abl:  # timing only: the epilogue's mask is a cheap function of (t, channel)
-        s = rep(s, "const unsigned b01 = dropout_bits2(key, t, co0), b23 = dropout_bits2(key, t, co0 + 2);",
-                "const unsigned b01 = (key ^ (t * 0x9E3779B9u)) + co0, b23 = b01 * 3u;")
+        s = rep(s, "b01 = dropout_bits2(skeys[rt >> 2], t, co0), b23 = dropout_bits2(skeys[rt >> 2], t, co0 + 2);",
+                "b01 = (skeys[rt >> 2] ^ (t * 0x9E3779B9u)) + co0, b23 = b01 * 3u;")
     if "nostats" in abl:  # timing only: no per-tile moment reductions
         s = rep(s, """      // reduce over the 16 rows of each lane group (lanes sharing h hold the same 4 channels)
       if (A.stats != nullptr) {""", """      if (A.stats != nullptr && s1[0] == 1234.5f) {""")

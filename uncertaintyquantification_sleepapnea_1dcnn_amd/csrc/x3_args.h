@@ -26,8 +26,8 @@ struct LayerArgs {
   double* stats;          // [G][16 slots][2][COUT] moment sums of R_l (nullptr: none)
   int n_win;              // windows per group
   int groups;
-  int tiles_per_group;    // informational (the kernel derives its tiling from n_win, groups and its tile size)
-  int total_tiles;
+  int tiles_per_group;    // x3_geo.h tiles_per_group, filled by the host for the grid clamp; the kernel derives
+  int total_tiles;        // the same from n_win, groups and its tile size and does not read either
   int in_shared;          // input indexed by window only (block-1 output shared by all passes)
   int sign_in;            // the input carries block l-1's dropout mask in its sign bits (else: hashed here)
   int sign_out;           // draw block l's mask in the epilogue, stored as the sign bit (blocks 2..5)

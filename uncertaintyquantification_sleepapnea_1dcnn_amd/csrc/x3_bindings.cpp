@@ -4,7 +4,6 @@
 #include "arch_tables.h"
 #include "bind_util.h"
 #include "x3_api.h"
-#include "x3_dense_map.h"
 
 namespace {
 using namespace apneauq::bind;
@@ -29,13 +28,12 @@ void x3_layer(int64_t layer, const at::Tensor& in, at::Tensor& out, const at::Te
   TORCH_CHECK(n_win >= 1 && groups >= 1, "x3_layer: empty launch");
   const int cin = kCh[layer], cout = kCh[layer + 1], ks = kKs[layer];
   const int64_t samples = n_win * groups, samples_in = in_shared ? n_win : samples;
-  const int ts = apneauq::x3_tile_samples((int)layer);
-  // dense_rows: tiles of 64 ts consecutive rows of the group's dense row space (60 per window) instead
-  // of ts whole 64-row window slots (csrc/x3_dense_map.h); the batch-moment kernels of a layer that has it
-  TORCH_CHECK(!dense_rows || apneauq::x3_has_dense((int)layer), "x3_layer: layer ", layer,
-              " has no dense-row kernel");
+  const apneauq::x3::LayerInfo info = apneauq::x3_layer_info((int)layer);
+  // dense_rows: tiles of 64 S consecutive rows of the group's dense row space (60 per window) instead
+  // of S whole 64-row window slots (csrc/x3_dense_map.h); the batch-moment kernels of a layer that has it
+  TORCH_CHECK(!dense_rows || info.has_dense, "x3_layer: layer ", layer, " has no dense-row kernel");
   TORCH_CHECK(!dense_rows || n_win < (int64_t(1) << 24), "x3_layer: too many windows for dense rows");
-  const int64_t tpg = dense_rows ? apneauq::x3::dense::tiles(n_win, 64 * ts) : (n_win + ts - 1) / ts;
+  const int64_t tpg = apneauq::x3::tiles_per_group<int64_t>(dense_rows, n_win, info.S);  // the kernel's tile walk
   TORCH_CHECK(tpg * groups < (int64_t(1) << 31), "x3_layer: too many tiles");
   const int64_t wgroups = w_gstride ? groups : 1, pgroups = p_gstride ? groups : 1;
   need(in, at::kFloat, samples_in * 60 * cin, "x3_layer: in");
@@ -104,7 +102,7 @@ void x3_layer(int64_t layer, const at::Tensor& in, at::Tensor& out, const at::Te
   A.pass_base = (unsigned)pass_base;
   A.window_offset = (unsigned)window_offset;
   A.seed = (unsigned long long)seed;
-  int g = grid > 0 ? (int)grid : num_cus(in) * apneauq::x3_wg_per_cu((int)layer);
+  int g = grid > 0 ? (int)grid : num_cus(in) * info.WPC;
   if (g > A.total_tiles) g = A.total_tiles;
   check(apneauq::x3_launch_layer((int)layer, A, g, dense_rows, cur_stream()), "x3_layer");
 }
@@ -191,8 +189,7 @@ void x3_head(const at::Tensor& sums, const at::Tensor& aff, int64_t aff_gstride,
   check(apneauq::x3_launch_head(A, cur_stream()), "x3_head");
 }
 
-int64_t x3_lds(int64_t layer) { return apneauq::x3_lds_bytes((int)layer); }
-bool x3_has_dense(int64_t layer) { return apneauq::x3_has_dense((int)layer); }
+bool x3_has_dense(int64_t layer) { return apneauq::x3_layer_info((int)layer).has_dense; }
 
 }  // namespace
 
@@ -209,7 +206,6 @@ TORCH_LIBRARY_FRAGMENT(apneauq, m) {
         "Tensor(d!)? amax=None, Tensor(e!)? gscale=None, bool running=False) -> ()");
   m.def("x3_head(Tensor sums, Tensor aff, int aff_gstride, Tensor dw, Tensor db, int p_gstride, Tensor(a!) out, "
         "int n_win, int groups, bool logits) -> ()");
-  m.def("x3_lds(int layer) -> int", &x3_lds);
   m.def("x3_has_dense(int layer) -> bool", &x3_has_dense);
 }
 

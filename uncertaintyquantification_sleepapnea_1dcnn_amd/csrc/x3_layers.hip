@@ -26,39 +26,28 @@
 //   head_kernel    logit = b + (1/60) sum_c w_c (s_c S1_c + t_c S0_c)  (BN 6 + dropout 6 + GAP + Dense
 //                  are linear per channel), p = sigmoid(logit)
 //
-// Layer kernel geometry (CDNA4-first):
-//   * one persistent workgroup per CU (7-8 MFMA waves + 4 loader waves) walks a contiguous range of
-//     tiles; a tile = S (2 or 4) samples of one group (MC-Dropout pass or ensemble member) = 64 S GEMM
-//     rows, every sample a 64-row slot (60 time steps + 4 zero rows, the 'same' padding halo);
-//   * dense rows (DENSE, the batch-moment kernels of blocks 2..5, picked per call): the tile is 64 S
-//     consecutive rows of the group's dense row space instead (row d = window d / 60, step d % 60), so
-//     none of its GEMM rows is a halo row: 6.25 % fewer tiles at the same wave tiling, accumulators and
-//     tile size.  A tile starts anywhere inside a window.  In LDS the windows it touches (at most 4 / 6
-//     for 128 / 256 rows) keep fixed 64-row slots relative to the first one, so the zero rows never
-//     move and are never written (a compact layout would have to re-zero them every chunk); the staging
+// Layer kernel (CDNA4-first).  Its geometry (tiles, waves, staging units, the LDS carve, the layer table) is
+// stated once in x3_geo.h and checked on the host (tests/x3_geo_check.cpp); what that header does not say:
+//   * one persistent workgroup per CU (7-8 MFMA waves + 4 loader waves) walks a contiguous range of tiles;
+//   * dense rows (DENSE, the batch-moment kernels of blocks 2..5, picked per call): 6.25 % fewer tiles at the
+//     same wave tiling, accumulators and tile size.  A tile starts anywhere inside a window; the staging
 //     writes the tile's rows plus up to PAD rows past either edge where their window also owns a row of
 //     the tile, and the B-fragment address of a lane's row tile is 4 rows further down per window
 //     boundary crossed (one register per row tile, recomputed per chunk).  What staging and epilogue need
-//     per row (LDS row, validity, the dropout mask words key ^ (t << 9) of the input and output streams)
-//     depends on (tile, row) only: the staging waves write it once per tile, one thread per row, into
-//     two small LDS tables that every chunk and channel tile looks up, and global rows are addressed
-//     linearly from the tile's first row (profiles/x3_row_descriptors.md).  Stored outputs are bitwise
+//     per row is looked up in two small LDS tables the staging waves write once per tile, and global rows are
+//     addressed linearly from the tile's first row (profiles/x3_row_descriptors.md).  Stored outputs are bitwise
 //     those of the slot mapping (the k-order of an output element does not depend on the row tile that
 //     holds it); only the grouping of the fp32 per-tile moment partials differs.  Index map:
-//     x3_dense_map.h; measurements: profiles/x3_dense_rows.md.  Block 6 (per-sample masked sums) and the
-//     per-sample-prescale variants (bitwise chunk invariance, whole-slot prescale) keep slots;
+//     x3_dense_map.h; measurements: profiles/x3_dense_rows.md;
 //   * the epilogue runs on every MFMA wave of the workgroup at once (the matrix pipe idles meanwhile), so the
 //     dense-row kernels keep it short: every channel tile's bias is loaded and waited for ahead of the first
-//     store, so that no memory wait stands between the stores of a tile (they used to be acknowledged one
-//     by one), and where a layer's loader waves have the slack (block 5, mask_tab_layer) they draw the output
-//     mask during the main loop into an LDS bit table that the epilogue only applies to the sign bit
-//     (profiles/x3_epilogue_offload.md);
-//   * the input channels stream through LDS in chunks of 32, double-buffered: while the MFMA waves
+//     store, so that no memory wait stands between the stores of a tile, and where a layer's loader waves have
+//     the slack (block 5, mask_tab_layer) they draw the output mask during the main loop into an LDS bit table
+//     that the epilogue only applies to the sign bit (profiles/x3_epilogue_offload.md);
+//   * the input channels stream through LDS in chunks, double-buffered: while the MFMA waves
 //     consume chunk c, the loader waves write chunk c+1 (BN affine + dropout + fp16 split of registers
 //     loaded one chunk earlier) and issue the HBM loads of chunk c+2; one LDS-only barrier per chunk,
 //     no vmcnt drain, and no HBM load ever queued in front of an MFMA wave's weight loads;
-//   * LDS row = [hi 32 ch | lo 32 ch | 32 B pad] = 160 B = 10 16-B slots (stride = 2 mod 4 slots: the
-//     ds_read_b128 lane groups of a 16x16x32 B fragment hit 16 distinct slots at any row offset);
 //   * conv = implicit GEMM  D[co][row] = sum_{tap, ci} W[tap][ci][co] A[row + tap - pad][ci]: weights are
 //     the A operand (host-packed fragments, one 1-KiB coalesced load per fragment, prefetched one k-step
 //     ahead), activations the B operand (LDS).  Waves tile rows x output channels (WM x WN) per layer so
@@ -67,19 +56,11 @@
 #include "f16x3.h"
 #include "x3_api.h"
 #include "x3_dense_map.h"
+#include "x3_geo.h"
 
 namespace apneauq {
 namespace x3 {
 
-// Staging waves of a layer without loader waves: the HBM loads of the next chunk are issued by MFMA
-// waves 0..kStagers-1 only (one per SIMD), so that the partner wave keeps the matrix pipe busy while the
-// stager's in-order vmcnt holds it at its next weight-fragment wait.
-constexpr int kStagers = 4;
-constexpr int kL = 60, kSR = 64, kHalo = 4;
-// A chunk = CK input channels (32 or 64) of the tile's rows; LDS row: hi 2CK B | lo 2CK B | pad 32 B
-// (row stride 2 mod 4 16-B slots for either CK).  Layers with few taps take 64-channel chunks: twice the
-// k-steps per chunk barrier.
-__host__ __device__ constexpr int row_bytes(int ck) { return 4 * ck + 32; }
 // Range-safe fp16 split.  The staging splits a = s_c R + t_c (BN affine x dropout rescale, R >= 0) into
 // fp16 hi + lo, which needs |a| < 65504 (hi finite) and |a| well above 2^-14 (lo normal).  Per SAMPLE
 // (the rows of one window in one pass / member), |a| <= max_c |s_c| * max R + max_c |t_c| =: b, so the
@@ -91,31 +72,6 @@ __host__ __device__ constexpr int row_bytes(int ck) { return 4 * ck + 32; }
 // per-sample tracking in the producer's epilogue (the moments are global, so this is invariant too).
 __device__ __forceinline__ int sample_prescale(unsigned rmax_bits, const float* amax) {
   return prescale_exp(__builtin_fmaf(amax[0], __uint_as_float(rmax_bits), amax[1]));
-}
-
-// per tile of S samples (S x 64 GEMM rows): LDS rows, chunk-buffer bytes, staged rows, 16-B staging units
-__host__ __device__ constexpr int lds_rows(int S) { return kHalo + S * kSR + kHalo; }
-__host__ __device__ constexpr int buf_bytes(int S, int ck) { return lds_rows(S) * row_bytes(ck); }
-// + per-workgroup fp64 moment sums [2][COUT]
-// two LDS chunk buffers, the workgroup's fp64 moment sums, and the epilogue down-scale factors of the
-// two most recently staged tiles ([2][S] floats, written by the staging waves)
-// (dense-row tiles: the slots of every window a tile can touch, x3_dense_map.h), and the row tables of
-// the two most recently staged tiles (written by the staging waves): [2][64 S] output-mask words of the
-// tile's rows, [2][tab_rows] descriptor and input-mask word of every staged row
-__host__ __device__ constexpr int tab_rows(int S, int ks) { return kSR * S + (ks - 1); }  // the tile's rows + 2 PAD
-// and, where a dense-row layer has loader waves (mask_tab), the output keep-bits of the current tile, drawn by
-// them: [64 S rows][cout / 16] 16-bit words, bit c % 16 of word c / 16 = keep (row, channel c)
-__host__ __device__ constexpr int mask_tab_bytes(int S, int cout) { return kSR * S * (cout / 16) * 2; }
-// The layers that do so: a dense-row kernel with loader waves where it measured faster, which is block 5
-// (96 -> 256, k 9: +1 %).  Block 3 (192 -> 224, k 3: 18 k-steps per tile and the most VALU per MFMA of all
-// layers) lost 0.5 - 2.4 % with the same draw on its loader waves, and block 4's mask stays with its consumer
-// (profiles/x3_epilogue_offload.md); the code below is written for any of them.
-__host__ __device__ constexpr bool mask_tab_layer(int cin, int cout, int ks, int lw, bool dense_rows) {
-  return dense_rows && lw > 0 && cin == 96 && cout == 256 && ks == 9;
-}
-__host__ __device__ constexpr int lds_bytes(int S, int cout, int ck, int ks, bool dense_rows = false, bool mask_tab = false) {
-  return 2 * (dense_rows ? dense::lds_rows(kSR * S) * row_bytes(ck) : buf_bytes(S, ck)) + 2 * cout * 8 + 2 * S * 4 +
-         (dense_rows ? 2 * kSR * S * 4 + 2 * tab_rows(S, ks) * 8 : 0) + (dense_rows && mask_tab ? mask_tab_bytes(S, cout) : 0);
 }
 
 // global-address-space load (keeps global_load_*, never flat_*)
@@ -139,93 +95,29 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// Waves: WM x WN MFMA waves, plus LW loader waves (LW > 0) that do all the input staging: HBM loads of
-// chunk c+2, BN affine + dropout + fp16 split of chunk c+1 into LDS.  vmcnt retires in order, so an MFMA
-// wave that issued HBM loads would stall its next weight-fragment wait on them; loader waves take that
-// latency instead, and wait at the chunk barrier without using issue slots.
-// Register budget: the waves of WPC workgroups per CU over the 4 SIMDs, at least 2 per SIMD.
-// A single workgroup of <= 4 waves per CU runs one wave per SIMD with the whole 512-register file
-// (VGPR + AGPR): accumulators of twice the rows per weight fragment.
-template <int NW, int WPC>
-constexpr int waves_per_eu() { return NW * WPC > 8 ? (NW * WPC + 3) / 4 : NW * WPC <= 4 ? 1 : 2; }
-// LW > 0: LW loader waves; LW <= 0: no loaders, MFMA waves 0 .. -LW-1 stage (LW = 0: kStagers of them)
-constexpr int loaders(int lw) { return lw > 0 ? lw : 0; }
-// PS: the per-sample prescale (moving statistics) is compiled in; without it (batch moments: per-group
-// prescale folded into the affine) the kernel has the registers of its tracking for other uses.
-// DENSE: the tile is 64 S consecutive rows of the group's dense row space (window d / 60, step d % 60)
-// instead of S whole 64-row sample slots: no GEMM row is a halo row (x3_dense_map.h).
+// One layer of blocks 2..6 on a persistent workgroup; the template parameters are a row of the layer table and
+// every constant derived from them is Cfg's (x3_geo.h).
 template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS, bool DENSE = false>
 __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN + loaders(LW), WPC>())) void layer_kernel(
     const LayerArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NWM = WM * WN, NW = NWM + loaders(LW), kThreads = NW * 64;
-  constexpr int kCK = CK, kRowB = row_bytes(CK), NQ = CK / 32, kQ = CK / 4;  // 32-ch sub-chunks, quads / row
-  constexpr int PAD = (KS - 1) / 2, kRows = kSR * S;  // GEMM rows per tile
-  static_assert(!DENSE || (!PS && !LAST), "dense rows: batch-moment blocks 2..5 only");
-  constexpr int kS = S, kBufB = DENSE ? dense::lds_rows(kRows) * kRowB : buf_bytes(S, CK);
-  // staged rows per chunk: the samples' time steps (dense rows: every row of the tile, see kMainU)
-  constexpr int kValidRows = DENSE ? kRows : S * kL, kUnits = kValidRows * kQ;
-  // staging waves: the LW loader waves, else MFMA waves 0..SW-1 (one per SIMD by default)
-  constexpr int SW = LW > 0 ? LW : LW < 0 ? (-LW < NW ? -LW : NW) : (kStagers < NW ? kStagers : NW);
-  constexpr int kSBase = LW > 0 ? NWM * 64 : 0;              // first staging thread
-  constexpr int kST = SW * 64;                                // staging threads
-  // 16-B staging units per staging thread.  Dense rows: kMainU units tile the rows of the tile exactly,
-  // and one more holds the PAD edge rows either side of it, on the first staging wave(s) only
-  constexpr int kMainU = (kUnits + kST - 1) / kST, kNU = kMainU + (DENSE ? 1 : 0);
-  constexpr int kEdgeWaves = (2 * PAD * kQ + 63) / 64;
-  static_assert(!DENSE || (kUnits % kST == 0 && kEdgeWaves <= SW), "dense rows: whole staging steps per tile");
-  static_assert(kST % kQ == 0 && (CK == 32 || CK == 64), "a staging thread keeps one channel quad");
-  constexpr int NCH = CIN / kCK, NCTA = COUT / 16, NCT = NCTA / WN, NRT = 4 * S / WM;
-  constexpr int NSTEP = NCH * NQ * KS;  // k-steps (32 input channels x one tap) per tile
-  // MFMA issue order: row tiles in groups of RG so that >= 4 accumulators rotate (dependent-issue
-  // latency); B fragments double-buffered one group ahead when the accumulators leave room
-  constexpr int RG = NCT >= 4                        ? 1
-                     : (NCT >= 3 && NCT * NRT > 16)    ? 1
-                     : NCT == 1                        ? 4
-                                                       : 2;
-  constexpr bool BDB = NCT * NRT <= 24 && RG < 4;
-  static_assert(NRT % RG == 0, "row-tile groups");
-  constexpr long long FRAG_STEP = (long long)NCTA * 128;  // f16x8 per (chunk, tap) k-step
-  static_assert(CIN % kCK == 0 && COUT % 16 == 0, "channel tiling");
-  static_assert(NCTA % WN == 0 && (4 * S) % WM == 0, "wave tiling");
-  static_assert(NRT % 4 == 0, "whole 64-row sample slots per wave row (epilogue keys, block 6 sums)");
-  double* st = reinterpret_cast<double*>(smem + 2 * kBufB);  // [2][COUT] per-workgroup moment sums
-  // [tile & 1][sample of the tile]: wscale x 2^-sa, the epilogue's undo of both prescales
-  float* wsc = reinterpret_cast<float*>(smem + 2 * kBufB + 2 * COUT * 8);
-  // Row tables of the dense-row kernels (x3_dense_map.h).  What the staging and the epilogue need to know
-  // about a row depends on (tile, row) only, not on the chunk or the channel tile, so the staging waves
-  // compute it once per tile, one thread per row, and every chunk and channel tile looks it up:
-  //   stab[tile & 1][staged row]  descriptor (LDS row, step, window slot, valid), input-mask word key ^ (t << 9)
-  //   ektab[tile & 1][tile row]   output-mask word where the layer draws the block's mask (read by the epilogue,
-  //                               or by the loader waves that draw it for the epilogue: mtab below)
-  // A tile's tables are written with the last chunk of the tile before it (the first tile's before the
-  // first barrier): one chunk barrier ahead of their first reader, the staging of the tile's chunk 0, and
-  // a whole tile after the last reader of the tables they replace (tile - 2, the parity).  The slot
-  // kernels (block 6, per-sample prescale) keep their per-chunk index math: block 6 measured 0.8 % slower
-  // with the tables (profiles/x3_row_descriptors.md).
-  constexpr int kTabRows = tab_rows(S, KS);
-  static_assert(!DENSE || CIN / CK >= 2, "row tables: a tile's tables are written one chunk of the same workgroup ahead");
-  unsigned* ektab = reinterpret_cast<unsigned*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4);
-  uint2* stab = reinterpret_cast<uint2*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4 + 2 * kRows * 4);
-  // Output keep-bits of the current tile (mask_tab_layer).  Where the epilogue
-  // stores the block's mask in the sign bit (A.sign_out), the loader waves draw it during the tile's main
-  // loop, from the same ektab mask words and the same hash, and the epilogue only inserts the bits: no hash
-  // and no threshold compare on an MFMA wave.  mtab[row][COUT / 16]: bit c % 16 of word c / 16 keeps channel
-  // c, so the 16-bit word of an accumulator tile's row holds the lane's four bits at 4 h.  kMtT loader
-  // threads share a row, kMtW words each, kMtPhase of them per chunk iteration.
-  // One table, no parity, no barrier of its own.  Tile T's epilogue runs in the MFMA waves' iteration of its
-  // chunk NCH - 1, between the chunk barriers of iterations NCH - 2 and NCH - 1; the loaders write T's bits in
-  // their iterations of chunks 0 .. NCH - 2, so the last write is before the barrier ahead of the epilogue and
-  // the first one after the barrier behind the epilogue of tile T - 1 (a group change only adds barriers, on
-  // both sides alike).  That takes one iteration at least: NCH >= 2.  The ektab row read here was written one
-  // barrier or more earlier, and its parity is rewritten (tile T + 2) in iteration NCH - 2 of tile T + 1.
-  constexpr bool kMaskTab = mask_tab_layer(CIN, COUT, KS, LW, DENSE);
+  using C = Cfg<CIN, COUT, KS, S, WM, WN, LAST, LW, CK, WPC, PS, DENSE>;
+  constexpr int NWM = C::NWM, kThreads = C::kThreads, kCK = CK, kRowB = C::kRowB, NQ = C::NQ, kQ = C::kQ;
+  constexpr int PAD = C::PAD, kRows = C::kRows, kS = S, kBufB = C::kBufB, kValidRows = C::kValidRows;
+  constexpr int SW = C::SW, kSBase = C::kSBase, kST = C::kST, kMainU = C::kMainU, kNU = C::kNU;
+  constexpr int NCH = C::NCH, NCT = C::NCT, NRT = C::NRT, NSTEP = C::NSTEP, RG = C::RG, kSP = C::kSP;
+  constexpr bool BDB = C::BDB;
+  constexpr long long FRAG_STEP = C::FRAG_STEP;
+  constexpr int kTabRows = C::kTabRows;
+  constexpr bool kMaskTab = C::kMaskTab;
   constexpr bool kBiasHoist = DENSE;  // the epilogue loads every channel tile's bias ahead of its first store
-  constexpr int kMtRowW = COUT / 16, kMtT = kMaskTab ? kST / kRows : 1, kMtW = kMtRowW / kMtT;
-  constexpr int kMtPhase = (kMtW + (NCH > 1 ? NCH - 2 : 0)) / (NCH > 1 ? NCH - 1 : 1);
-  static_assert(!kMaskTab || NCH >= 2, "mask table: written in the chunk iterations ahead of the tile's last");
-  static_assert(!kMaskTab || (kST % kRows == 0 && kMtRowW % kMtT == 0), "mask table: whole words per loader thread");
-  unsigned short* mtab = reinterpret_cast<unsigned short*>(smem + 2 * kBufB + 2 * COUT * 8 + 2 * S * 4 + 2 * kRows * 4 + 2 * kTabRows * 8);
+  constexpr int kMtRowW = C::kMtRowW, kMtT = C::kMtT, kMtW = C::kMtW, kMtPhase = C::kMtPhase;
+  // the LDS carve (x3_geo.h): moment sums, epilogue factors, and the dense-row kernels' row and mask tables
+  double* st = reinterpret_cast<double*>(smem + C::st);
+  float* wsc = reinterpret_cast<float*>(smem + C::wsc);
+  unsigned* ektab = reinterpret_cast<unsigned*>(smem + C::ektab);
+  uint2* stab = reinterpret_cast<uint2*>(smem + C::stab);
+  unsigned short* mtab = reinterpret_cast<unsigned short*>(smem + C::mtab);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -235,30 +127,20 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   APNEAUQ_DASSERT(blockDim.x == kThreads);
 
   const int wg = xcd_order(blockIdx.x, gridDim.x);
-  // tiles per group at this kernel's tile size
-  const int tpg = DENSE ? (int)dense::tiles(A.n_win, kRows) : (A.n_win + S - 1) / S;
+  // the tile walk (x3_geo.h): tiles per group at this kernel's tile size, this workgroup's tiles
+  const int tpg = tiles_per_group(DENSE, A.n_win, S);
   const int total_tiles = tpg * A.groups;
-  const int t_begin = (int)((long long)wg * total_tiles / gridDim.x);
-  const int t_end = (int)((long long)(wg + 1) * total_tiles / gridDim.x);
+  const int t_begin = tile_begin(wg, total_tiles, gridDim.x), t_end = tile_begin(wg + 1, total_tiles, gridDim.x);
   if (t_begin >= t_end) return;  // workgroup-uniform
   const int slot = wg % kStatSlots;
 
-  // ---- staging: staging thread i = tid - kSBase keeps the 16-B units (row ri = i/8 + kST/8 u,
-  // channel quad q = i % 8) of every chunk
+  // ---- staging: staging thread i = tid - kSBase keeps the same 16-B units (C::slot_unit_row / C::unit_row,
+  // channel quad q = i % kQ) of every chunk
   const bool loader = LW > 0 && wave >= NWM;
   const bool stager = LW > 0 ? loader : wave < SW;
-  const bool edge_wave = DENSE && wave >= kSBase / 64 && wave - kSBase / 64 < kEdgeWaves;  // wave-uniform
-  // dense rows, unit u of staging thread tid: its row relative to the tile's first row (the edge unit holds
-  // the PAD rows either side of the tile); false where the thread has no such unit
-  auto unit_row = [&](int u, int tid, int& rel) -> bool {
-    const int r = tid / kQ;
-    if (u < kMainU) {
-      rel = r + (kST / kQ) * u;
-      return true;
-    }
-    rel = r < PAD ? r - PAD : kRows - PAD + r;
-    return edge_wave && r < 2 * PAD;
-  };
+  // C::edge_wave(wave), written out: the call in its place changes the schedule of the three dense-row kernels
+  // with loader waves (profiles/x3_geo_refactor.md); the host check holds the two against each other
+  const bool edge_wave = DENSE && wave >= kSBase / 64 && wave - kSBase / 64 < C::kEdgeWaves;  // wave-uniform
   // staging register set: the chunk's 16-B units + the BN affine (scale, shift) x 1/(1-p) of the
   // thread's 4 channels
   struct Stage {
@@ -278,24 +160,15 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   unsigned skeys[kS];
   unsigned skey_tile = 0u;  // the tile's stream key
   // prescale exponents sa of the staging tile's samples, one signed byte each (4 per register)
-  static_assert(kS <= 8, "packed per-sample exponents");
-  constexpr int kSP = (kS + 3) / 4;
   unsigned sa_pack[kSP];
-  // first window / first dense row of a tile, its first window wf, its start inside it, and the rows from
-  // its first row to the end of the group (clamped: only rows of the tile are compared with it)
-  struct Geo {
-    int g, w0, wf, off, rows_left;
-  };
-  auto tile_geo = [&](int tile) {
-    Geo G;
-    G.g = tile / tpg;
-    G.w0 = (tile - G.g * tpg) * (DENSE ? kRows : kS);
-    G.wf = DENSE ? G.w0 / kL : G.w0, G.off = DENSE ? G.w0 - G.wf * kL : 0;
-    const long long left = (long long)(A.n_win - G.wf) * kL - G.off;
-    G.rows_left = (int)(left < 1024 ? left : 1024);
-    return G;
-  };
+  auto tile_geo = [&](int tile) { return x3::tile_geo<DENSE, S>(tile, tpg, A.n_win); };
   const bool mask_out = DENSE && A.sign_out && A.thr_out != 0u;  // the epilogue draws block l's mask
+  // The row tables of tile `tile` (x3_geo.h stab, ektab), one staging thread per row.  A tile's tables are
+  // written with the last chunk of the tile before it (the first tile's before the first barrier): one chunk
+  // barrier ahead of their first reader, the staging of the tile's chunk 0, and a whole tile after the last
+  // reader of the tables they replace (tile - 2, the parity).  The slot kernels (block 6, per-sample
+  // prescale) keep their per-chunk index math: block 6 measured 0.8 % slower with the tables
+  // (profiles/x3_row_descriptors.md).
   auto write_tables = [&](int tile) {
     if constexpr (DENSE) {
       const int tid = opaque_tid() - kSBase;
@@ -315,9 +188,18 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       }
     }
   };
-  // loader waves, iteration of chunk c < NCH - 1 of the tile: words c kMtPhase .. of the thread's kMtW words
-  // of the tile's keep-bit table; bits 2 p, 2 p + 1 of a word are the two halves of mix32(kt ^ (8 word + p)),
-  // the epilogue's dropout_bits2(key, t, 16 word + 2 p)
+  // Output keep-bits of the current tile (kMaskTab, x3_geo.h mtab).  Where the epilogue stores the block's mask
+  // in the sign bit (A.sign_out), the loader waves draw it during the tile's main loop, from the same ektab mask
+  // words and the same hash, and the epilogue only inserts the bits: no hash and no threshold compare on an
+  // MFMA wave.  One table, no parity, no barrier of its own.  Tile T's epilogue runs in the MFMA waves'
+  // iteration of its chunk NCH - 1, between the chunk barriers of iterations NCH - 2 and NCH - 1; the loaders
+  // write T's bits in their iterations of chunks 0 .. NCH - 2, so the last write is before the barrier ahead of
+  // the epilogue and the first one after the barrier behind the epilogue of tile T - 1 (a group change only adds
+  // barriers, on both sides alike).  The ektab row read here was written one barrier or more earlier, and its
+  // parity is rewritten (tile T + 2) in iteration NCH - 2 of tile T + 1.
+  // Iteration of chunk c < NCH - 1 of the tile: words c kMtPhase .. of the thread's kMtW words; bits 2 p,
+  // 2 p + 1 of a word are the two halves of mix32(kt ^ (8 word + p)), the epilogue's
+  // dropout_bits2(key, t, 16 word + 2 p)
   auto draw_mask = [&](int tile, int c) {
     if constexpr (kMaskTab) {
       const int tid = opaque_tid() - kSBase, row = tid / kMtT, w0 = (tid % kMtT) * kMtW;
@@ -352,7 +234,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
 #pragma unroll
       for (int u = 0; u < kNU; ++u) {
         int rel;
-        bool have = unit_row(u, tid, rel);
+        bool have = C::unit_row(u, tid, edge_wave, rel);
         if (u >= kMainU) have = have && dense::staged(G.off + rel, G.off, kRows, PAD);
         R.v[u] = f32x4{-0.f, -0.f, -0.f, -0.f};
         if (have && rel < G.rows_left) R.v[u] = gld<f32x4>(in + rel * CIN);
@@ -360,7 +242,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
     } else {
 #pragma unroll
       for (int u = 0; u < kNU; ++u) {
-        const int ri = tid / kQ + (kST / kQ) * u;
+        const int ri = C::slot_unit_row(u, tid);
         R.v[u] = f32x4{-0.f, -0.f, -0.f, -0.f};
         if (ri < kValidRows) {
           const int s = ri / kL, t = ri - s * kL, w = G.w0 + s;
@@ -374,8 +256,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   };
   auto store_chunk = [&](int tile, int c, char* buf, const Stage& R) {
     const int tid = opaque_tid() - kSBase, q = tid % kQ;
-    const int g = tile / tpg;
-    const int w0 = (tile - g * tpg) * (DENSE ? kRows : kS);
+    const Geo G = tile_geo(tile);
+    const int g = G.g, w0 = G.w0;
     // the next tile's tables, one chunk barrier before the staging of its first chunk reads them
     if (DENSE && c == NCH - 1 && tile + 1 < t_end) write_tables(tile + 1);
     if (tile != key_tile) {  // workgroup-uniform
@@ -411,12 +293,12 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
       unsigned kt = 0u;  // the row's input-mask word key ^ (t << 9)
       if constexpr (DENSE) {
         int rel;
-        if (!unit_row(u, tid, rel)) continue;
+        if (!C::unit_row(u, tid, edge_wave, rel)) continue;
         const uint2 e = tab[rel];  // the row's descriptor and mask word
         if (e.x == 0u) continue;   // a row that is not staged (an LDS row is >= kHalo)
         s = dense::desc_slot(e.x), lrow = dense::desc_lds_row(e.x), valid = dense::desc_valid(e.x), kt = e.y;
       } else {
-        const int ri = tid / kQ + (kST / kQ) * u;
+        const int ri = C::slot_unit_row(u, tid);
         if (ri >= kValidRows) continue;
         s = ri / kL;
         const int t = ri - s * kL;
@@ -571,8 +453,8 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   // ---- epilogue of one tile: bias + ReLU, moments, block-l dropout, store / per-sample sums
   auto epilogue = [&](int tile) {
     const int lane = opaque_tid() & 63, m = lane & 15, h = lane >> 4;
-    const int g = tile / tpg;
-    const int w0 = (tile - g * tpg) * (DENSE ? kRows : kS);  // first window / first dense row of the tile
+    const Geo G = tile_geo(tile);
+    const int g = G.g, w0 = G.w0;  // the tile's group, its first window / first dense row
     // undo the weight prescale 2^sw and each sample's activation prescale 2^sa (exact powers of two;
     // the factors were put in LDS by the staging waves)
     float wsq[NRT / 4];
@@ -749,7 +631,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   //   iteration it: compute chunk it from buf[it & 1]; staging waves write chunk it+1 (loaded into
   //   registers one iteration earlier) into buf[(it+1) & 1] mid-way; barrier; issue the loads of it+2.
   // buf[(it+1) & 1] was last read by compute(it-1), which every wave finished before barrier(it-1).
-  for (int i = tid; i < 2 * kBufB / 16; i += kThreads) reinterpret_cast<f32x4*>(smem)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = tid; i < C::st / 16; i += kThreads) reinterpret_cast<f32x4*>(smem)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int i = tid; i < 2 * COUT; i += kThreads) st[i] = 0.0;
   if (DENSE && stager) write_tables(t_begin);
   __syncthreads();
@@ -758,6 +640,16 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
   // dense rows: the tile's start inside its first window
   auto tile_off = [&](int tile) { return DENSE ? (int)((long long)(tile % tpg) * kRows % kL) : 0; };
   int g_cur = t_begin / tpg;
+  // a tile's first chunk: the moment sums go out when the tile starts another group (workgroup-uniform)
+  auto group_change = [&](int tile, int c) {
+    if (c == 0) {
+      const int g = tile / tpg;
+      if (g != g_cur) {
+        flush_stats(g_cur);
+        g_cur = g;
+      }
+    }
+  };
   if constexpr (LW > 0) {
     // Loader and MFMA waves run the same barrier sequence: one LDS barrier before the first chunk and
     // after every chunk, and the two of flush_stats at every group change and at the end.
@@ -773,13 +665,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
 #pragma unroll 1
       for (int it = 0; it < total; ++it) {
         const int tile = chunk_tile(it), c = it - (tile - t_begin) * NCH;
-        if (c == 0) {
-          const int g = tile / tpg;
-          if (g != g_cur) {
-            flush_stats(g_cur);
-            g_cur = g;
-          }
-        }
+        group_change(tile, c);
         // chunk it+1 into the buffer compute(it-1) read (every wave passed the barrier after it)
         if (stager && it + 1 < total) store_chunk(chunk_tile(it + 1), (it + 1) % NCH, smem + ((it + 1) & 1) * kBufB, s0);
         // this tile's output keep-bits, a share per iteration ahead of its last (kMaskTab)
@@ -795,13 +681,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
 #pragma unroll 1
     for (int it = 0; it < total; ++it) {
       const int tile = chunk_tile(it), c = it - (tile - t_begin) * NCH;
-      if (c == 0) {
-        const int g = tile / tpg;
-        if (g != g_cur) {
-          flush_stats(g_cur);
-          g_cur = g;
-        }
-      }
+      group_change(tile, c);
       const gf16x8* wcur = wbase(tile);
       const gf16x8* wnxt = wbase(tile + 1 < t_end ? tile + 1 : tile);
       compute_chunk(c, tile_off(tile), smem + (it & 1) * kBufB, wcur, wnxt, []() {});
@@ -821,13 +701,7 @@ __global__ __launch_bounds__((WM * WN + loaders(LW)) * 64, (waves_per_eu<WM * WN
 #pragma unroll 1
   for (int it = 0; it < total; ++it) {
     const int tile = chunk_tile(it), c = it - (tile - t_begin) * NCH;
-    if (c == 0) {
-      const int g = tile / tpg;
-      if (g != g_cur) {
-        flush_stats(g_cur);
-        g_cur = g;
-      }
-    }
+    group_change(tile, c);
     const gf16x8* wcur = wbase(tile);
     const gf16x8* wnxt = wbase(tile + 1 < t_end ? tile + 1 : tile);
     char* buf = smem + (it & 1) * kBufB;
@@ -1025,27 +899,23 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs A) {
 // ------------------------------------------------------------------------------- launch helpers
 template <int CIN, int COUT, int KS, int S, int WM, int WN, bool LAST, int LW, int CK, int WPC, bool PS, bool DENSE = false>
 hipError_t launch_layer(const LayerArgs& A, int grid, hipStream_t stream) {
-  constexpr int lds = lds_bytes(S, COUT, CK, KS, DENSE, mask_tab_layer(CIN, COUT, KS, LW, DENSE));
-  static_assert(WPC * lds <= 160 * 1024, "LDS of the workgroups sharing a CU");
+  using C = Cfg<CIN, COUT, KS, S, WM, WN, LAST, LW, CK, WPC, PS, DENSE>;
   auto k = layer_kernel<CIN, COUT, KS, S, WM, WN, LAST, LW, CK, WPC, PS, DENSE>;
   static bool attr = false;
   if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C::bytes);
     if (e != hipSuccess) return e;
     attr = true;
   }
-  hipLaunchKernelGGL(k, dim3(grid), dim3((WM * WN + loaders(LW)) * 64), lds, stream, A);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(C::kThreads), C::bytes, stream, A);
   return hipGetLastError();
 }
 
-// the dense-row instantiation of a layer, compiled only where the layer table asks for it.  A layer
-// without loader waves (block 2) stages on all its MFMA waves there: the extra edge unit beside four
-// stagers' eight units and the NRT B-fragment bases spilled (52 B / lane), with eight stagers' five units
-// the kernel fits (253 VGPRs, no scratch).
+// the dense-row instantiation of a layer, compiled only where the layer table asks for it
 template <bool HAVE, int CIN, int COUT, int KS, int S, int WM, int WN, int LW, int CK, int WPC>
 hipError_t launch_dense(const LayerArgs& A, int grid, hipStream_t stream) {
   if constexpr (HAVE) {
-    return launch_layer<CIN, COUT, KS, S, WM, WN, false, (LW > 0 ? LW : -(WM * WN)), CK, WPC, false, true>(A, grid, stream);
+    return launch_layer<CIN, COUT, KS, S, WM, WN, false, dense_lw(LW, WM, WN), CK, WPC, false, true>(A, grid, stream);
   } else {
     return hipErrorInvalidValue;
   }
@@ -1053,67 +923,9 @@ hipError_t launch_dense(const LayerArgs& A, int grid, hipStream_t stream) {
 
 }  // namespace x3
 
-// Layer table of the reference architecture (cnn_baseline_train.py:59-86), blocks 2..6:
-//   <Cin, Cout, k, samples per tile, wave rows WM, wave channel groups WN, block 6, loader waves LW
-//    (<= 0: no loaders, -LW MFMA waves stage) with / LWB without the per-sample prescale,
-//    input channels per staged chunk CK, persistent workgroups per CU WPC, DENSE: the dense-row
-//    instantiation (batch moments, blocks 2..5) is compiled in and can be picked per call>
-// Each MFMA wave owns (4 S / WM) 16-row tiles x (Cout / 16 / WN) 16-channel tiles; the 64-accumulator-tile
-// layers (Cout 224 / 256) run 2-sample tiles so that the next k-step's weight fragments and the B
-// double-buffer fit beside the accumulators without spilling.  Loader waves (ablation table in
-// profiles/x3_loader_waves.md) on every layer but block 2, whose 96-accumulator tile needs the 256-VGPR
-// budget of 8 waves (loaders at 2-sample tiles: slower; at 4: 99 VGPRs spilled); its staging runs on
-// MFMA waves 0..3, or on all 8 where the per-sample prescale's registers would otherwise spill.  64-channel chunks for
-// blocks 3 and 6 (block 2 would spill; Cin 224 / 96 are not multiples of 64).  The Cout-96 blocks 4 and
-// 6 run 4 MFMA waves of 24 accumulator tiles (WM 2 x WN 2) rather than 8 of 12: each weight fragment
-// is re-read by 2 wave rows instead of 4 (their texture path was the busy one), -1.2 % MCD.
-// Measurements: profiles/x3_epilogue_ab_r3.md, profiles/x3_mask_side_r4.md.
-// A/B builds may substitute another table (APNEAUQ_X3_TABLE=<path.h> in csrc/build.py, tools/probes/x3_tables/):
-// every entry is a complete, correct configuration, only the speed differs.
-#ifdef APNEAUQ_X3_TABLE
-#include APNEAUQ_X3_TABLE
-#else
-#define APNEAUQ_X3_LAYERS(X)                           \
-  X(1, 128, 192, 5, 4, 2, 4, false, -8, 0, 32, 1, true) \
-  X(2, 192, 224, 3, 2, 1, 7, false, 4, 4, 64, 1, true)  \
-  X(3, 224, 96, 7, 4, 2, 2, false, 4, 4, 32, 1, true)   \
-  X(4, 96, 256, 9, 2, 1, 8, false, 4, 4, 32, 1, true)   \
-  X(5, 256, 96, 9, 4, 2, 2, true, 4, 4, 64, 1, false)
-#endif
+x3::LayerInfo x3_layer_info(int layer) { return x3::layer_info(layer); }
 
-int x3_lds_bytes(int layer) {
-#define APNEAUQ_X3_LDS(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
-  if (layer == L) return x3::lds_bytes(S, CO, CK, K);
-  APNEAUQ_X3_LAYERS(APNEAUQ_X3_LDS)
-#undef APNEAUQ_X3_LDS
-  return 0;
-}
-
-int x3_tile_samples(int layer) {
-#define APNEAUQ_X3_TS(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
-  if (layer == L) return S;
-  APNEAUQ_X3_LAYERS(APNEAUQ_X3_TS)
-#undef APNEAUQ_X3_TS
-  return 0;
-}
-
-// the layer has a dense-row instantiation (x3_launch_layer dense_rows)
-bool x3_has_dense(int layer) {
-#define APNEAUQ_X3_HD(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
-  if (layer == L) return DENSE && !LAST;
-  APNEAUQ_X3_LAYERS(APNEAUQ_X3_HD)
-#undef APNEAUQ_X3_HD
-  return false;
-}
-
-int x3_wg_per_cu(int layer) {
-#define APNEAUQ_X3_WPC(L, CI, CO, K, S, WM, WN, LAST, LW, LWB, CK, WPC, DENSE) \
-  if (layer == L) return WPC;
-  APNEAUQ_X3_LAYERS(APNEAUQ_X3_WPC)
-#undef APNEAUQ_X3_WPC
-  return 1;
-}
-
+// the kernels of the layer table (x3_geo.h)
 hipError_t x3_launch_layer(int layer, const x3::LayerArgs& A, int grid, bool dense_rows, hipStream_t stream) {
   using namespace x3;
   // the per-sample prescale variant only where it is used (moving statistics)

@@ -33,8 +33,7 @@ from . import _ext, fused, rng
 CH = fused.FUSED_CHANNELS
 KS = fused.FUSED_KSIZES
 STAT_SLOTS = 16  # csrc/x3_args.h kStatSlots
-TILE = 4         # samples per layer-kernel tile
-CK = 32          # input channels per staged chunk
+CK = 32          # input channels per packed weight-fragment chunk (one MFMA k-step)
 # bytes of activation workspace per sample: ping-pong fp32 buffers of 192 + 256 channels x 60 steps
 # (+ the block-1 output: per window for batch-BN MC Dropout, per window and member for the Deep Ensemble;
 # budgeted per sample, the conservative bound)
@@ -231,11 +230,57 @@ def _max_samples(dev, per_sample: int, frac: float = 0.45) -> int:
     other work (one 50-pass chunk of 16384 windows would hold ~88 GB).  Batch-BN MC Dropout over 16384
     windows, T = 50: 219.2-220.3 ms in one chunk (100 GB cap), 219.6-220.0 ms in 12-GB chunks
     (``profiles/x3_epilogue_ab_r3.md``): pass chunks of >= 30 k samples keep the launches full."""
-    import os
-
     free = torch.cuda.mem_get_info(dev)[0]
     cap = float(os.environ.get("APNEAUQ_X3_WS_GB", "20")) * 2 ** 30
     return max(1, int(min(free * frac, cap)) // per_sample)
+
+
+# The three launches the drivers below schedule.  Each derives in one place what follows from the model, the
+# layer index and the schedule's flags: ping-pong buffers, per-member strides, thresholds, prescale tensors.
+def _layer(model: X3Model, ws: "_Workspace", l: int, *, n: int, groups: int, dropout: bool, stats=None,
+           shared_r1: bool = False, pass_affines: bool = False, seed: int = 0, pass_base: int = 0,
+           window_offset: int = 0, grid: int = 0, prescale: str = "group", sign: frozenset = frozenset(),
+           dense: frozenset = frozenset()) -> None:
+    """Block l + 1 (l = 1..5) over ``groups`` x ``n`` samples, block l's affine ``ws.aff[l - 1]`` applied while
+    staging.  ``shared_r1``: every group reads the same block-1 output (the passes of one model).  ``pass_affines``:
+    each group has its own affines (batch moments) but block 1's; else one set per ensemble member.  ``prescale``:
+    ``"sample"`` -- range-safe split from per-sample maxima (reads block l's, tracks block l + 1's); ``"group"``
+    -- one power of two per group, folded into the affine.  ``sign`` / ``dense``: :func:`_sign_layers` /
+    :func:`_dense_layers` (empty: neither)."""
+    per_member = model.G > 1
+    src = ws.r1 if l == 1 else ws.buf[(l - 2) % 2]
+    dst = ws.sums if l == 5 else ws.buf[(l - 1) % 2]
+    thr = [rng.dropout_threshold(model.spec.blocks[i].dropout) if dropout else 0 for i in (l - 1, l)]
+    if prescale == "sample":
+        pre = (ws.smax[l - 1], ws.amax[l - 1], ws.smax_out(l, groups * n), None)
+    else:
+        pre = (None, None, None, ws.gscale[l - 1])
+    _ops().x3_layer(l, src, dst, model.wfrag[l], model.wfrag[l].shape[1] // 8 if per_member else 0, model.bias[l],
+                    model.wscale[l], CH[l + 1] if per_member else 0, ws.aff[l - 1],
+                    2 * CH[l] if per_member or (pass_affines and l > 1) else 0, stats, n, groups,
+                    bool(shared_r1 and l == 1), *thr, int(seed) & ((1 << 63) - 1), int(pass_base), int(window_offset),
+                    int(grid), *pre, *_sign(l, sign), l in dense)
+
+
+def _aff(model: X3Model, ws: "_Workspace", l: int, *, groups: int, dropout: bool, stats=None, update: bool = False,
+         repeat: int = 1, inv_count: float = 1.0, amax: bool = False, gscale: bool = False,
+         running: bool = False) -> None:
+    """BN affine of block l + 1 (l = 0..5) into ``ws.aff[l]``, times 1 / (1 - p) with ``dropout``: from the batch
+    moments ``stats`` (and the moving update, ``repeat`` times, with ``update``) or from the moving statistics (no
+    ``stats``, or ``running``: the stats then only bound the range).  ``amax`` / ``gscale``: also write the channel
+    maxima / the per-group prescale that the next block's range-safe split reads."""
+    g, b, mm, mv = model.bn[l]
+    _ops().x3_aff(stats, g, b, mm, mv, ws.aff[l], CH[l + 1], groups, CH[l + 1] if model.G > 1 else 0, bool(update),
+                  repeat, inv_count, float(model.spec.bn_epsilon), float(model.spec.bn_momentum),
+                  _dsc(model.spec.blocks[l].dropout) if dropout else 1.0, ws.amax[l] if amax else None,
+                  ws.gscale[l] if gscale else None, running)
+
+
+def _head(model: X3Model, ws: "_Workspace", *, n: int, groups: int, pass_affines: bool = False, logits: bool = False):
+    """BN 6 + dropout 6 + GAP + Dense + sigmoid of ``groups`` x ``n`` samples from ``ws.sums`` into ``ws.out``."""
+    per_member = model.G > 1
+    _ops().x3_head(ws.sums, ws.aff[5], 2 * CH[6] if per_member or pass_affines else 0, model.dw, model.db,
+                   CH[6] if per_member else 0, ws.out, n, groups, bool(logits))
 
 
 @torch.no_grad()
@@ -249,7 +294,7 @@ def mcd_batch(model: X3Model, x: torch.Tensor, n_pass: int, seed: int, pass_base
     (statistics are per pass, so chunking is exact; every rank must use the same chunking).  ``grid``:
     persistent workgroups per layer launch (0: one per CU)."""
     assert model.G == 1, "mcd_batch runs one model"
-    spec, o = model.spec, _ops()
+    o = _ops()
     x = x.to(device=model.device, dtype=torch.float32).contiguous()
     n = x.shape[0]
     gn = int(global_n or n)
@@ -277,39 +322,28 @@ def mcd_batch(model: X3Model, x: torch.Tensor, n_pass: int, seed: int, pass_base
     chunk = -(-n_pass // n_chunks)
     ws = model.workspace(chunk * n, n, chunk)
     inv_count = 1.0 / (gn * 60.0)
-    thr = [rng.dropout_threshold(b.dropout) for b in spec.blocks]
-    dsc = [_dsc(b.dropout) for b in spec.blocks]
-    eps, mom = float(spec.bn_epsilon), float(spec.bn_momentum)
-    seed = int(seed) & ((1 << 63) - 1)
-    sl = _sign_layers()
-    dl = _dense_layers()
+    sl, dl = _sign_layers(), _dense_layers()
     out = torch.empty(n_pass, n, dtype=torch.float32, device=model.device)
     # block 1 once: no dropout precedes it, so every pass sees the same R_1 and the same moments
     ws.stats[0].zero_()
     o.x3_l1(x, model.w1, model.b1, ws.r1, ws.stats[0], n, 1, None)
     if sync is not None:
         _sync_stats(sync, ws.stats[0], 1, CH[1])
-    g, b, mm, mv = model.bn[0]
-    o.x3_aff(ws.stats[0], g, b, mm, mv, ws.aff[0], CH[1], 1, 0, bool(update_moving), n_pass, inv_count, eps, mom, dsc[0],
-             None, ws.gscale[0])
+    _aff(model, ws, 0, groups=1, dropout=True, stats=ws.stats[0], update=update_moving, repeat=n_pass,
+         inv_count=inv_count, gscale=True)
     for t0 in range(0, n_pass, chunk):
         tc = min(chunk, n_pass - t0)
-        pb = int(pass_base) + t0
         for l in range(1, 6):
             c = CH[l + 1]
             st = ws.stats[l]
             st[: tc * STAT_SLOTS * 2 * c].zero_()
-            src = ws.r1 if l == 1 else ws.buf[(l - 2) % 2]
-            dst = ws.sums if l == 5 else ws.buf[(l - 1) % 2]
-            o.x3_layer(l, src, dst, model.wfrag[l], 0, model.bias[l], model.wscale[l], 0, ws.aff[l - 1],
-                       0 if l == 1 else 2 * CH[l], st, n, tc, l == 1, thr[l - 1], thr[l], seed, pb,
-                       int(window_offset), int(grid), None, None, None, ws.gscale[l - 1], *_sign(l, sl), l in dl)
+            _layer(model, ws, l, n=n, groups=tc, dropout=True, stats=st, shared_r1=True, pass_affines=True, seed=seed,
+                   pass_base=int(pass_base) + t0, window_offset=window_offset, grid=grid, sign=sl, dense=dl)
             if sync is not None:
                 _sync_stats(sync, st, tc, c)
-            g, b, mm, mv = model.bn[l]
-            o.x3_aff(st, g, b, mm, mv, ws.aff[l], c, tc, 0, bool(update_moving), 1, inv_count, eps, mom, dsc[l],
-                     None, ws.gscale[l])
-        o.x3_head(ws.sums, ws.aff[5], 2 * CH[6], model.dw, model.db, 0, ws.out, n, tc, False)
+            _aff(model, ws, l, groups=tc, dropout=True, stats=st, update=update_moving, inv_count=inv_count,
+                 gscale=True)
+        _head(model, ws, n=n, groups=tc, pass_affines=True)
         out[t0: t0 + tc].copy_(ws.out[: tc * n].view(tc, n))
     return out
 
@@ -326,18 +360,13 @@ def _mcd_batch_windowed(model: X3Model, x: torch.Tensor, n_pass: int, seed: int,
     (seed, block, pass, global window id), so the recomputed activations are the same numbers, and the
     result equals the one-shot schedule up to the order of the fp64 moment sums.  Cost: 21 block
     evaluations per pass instead of 6 (only beyond ~2 M windows per 288-GB GPU)."""
-    spec, o = model.spec, _ops()
+    o = _ops()
     n = x.shape[0]
     wc = max(1, int(max_samples))
     bounds = [(s, min(n, s + wc)) for s in range(0, n, wc)]
     ws = model.workspace(wc, wc, 1)
     inv_count = 1.0 / (gn * 60.0)
-    thr = [rng.dropout_threshold(b.dropout) for b in spec.blocks]
-    dsc = [_dsc(b.dropout) for b in spec.blocks]
-    eps, mom = float(spec.bn_epsilon), float(spec.bn_momentum)
-    seed = int(seed) & ((1 << 63) - 1)
-    sl = _sign_layers()
-    dl = _dense_layers()
+    sl, dl = _sign_layers(), _dense_layers()
     out = torch.empty(n_pass, n, dtype=torch.float32, device=model.device)
 
     def run(s: int, e: int, upto: int, pb: int, stats_layer: int) -> None:
@@ -345,19 +374,15 @@ def _mcd_batch_windowed(model: X3Model, x: torch.Tensor, n_pass: int, seed: int,
         m = e - s
         o.x3_l1(x[s:e], model.w1, model.b1, ws.r1, ws.stats[0] if stats_layer == 0 else None, m, 1, None)
         for l in range(1, upto + 1):
-            src = ws.r1 if l == 1 else ws.buf[(l - 2) % 2]
-            dst = ws.sums if l == 5 else ws.buf[(l - 1) % 2]
-            o.x3_layer(l, src, dst, model.wfrag[l], 0, model.bias[l], model.wscale[l], 0, ws.aff[l - 1],
-                       0 if l == 1 else 2 * CH[l], ws.stats[l] if l == stats_layer else None, m, 1, l == 1,
-                       thr[l - 1], thr[l], seed, pb, int(window_offset) + s, 0, None, None, None, ws.gscale[l - 1],
-                       *_sign(l, sl), l in dl)
+            _layer(model, ws, l, n=m, groups=1, dropout=True, stats=ws.stats[l] if l == stats_layer else None,
+                   shared_r1=True, pass_affines=True, seed=seed, pass_base=pb, window_offset=int(window_offset) + s,
+                   sign=sl, dense=dl)
 
     def finish_layer(l: int, repeat: int) -> None:
         if sync is not None:
             _sync_stats(sync, ws.stats[l], 1, CH[l + 1])
-        g, b, mm, mv = model.bn[l]
-        o.x3_aff(ws.stats[l], g, b, mm, mv, ws.aff[l], CH[l + 1], 1, 0, bool(update_moving), repeat, inv_count, eps,
-                 mom, dsc[l], None, ws.gscale[l])
+        _aff(model, ws, l, groups=1, dropout=True, stats=ws.stats[l], update=update_moving, repeat=repeat,
+             inv_count=inv_count, gscale=True)
 
     # block 1: no dropout before it, so its moments (and affine) are shared by every pass
     ws.stats[0].zero_()
@@ -373,7 +398,7 @@ def _mcd_batch_windowed(model: X3Model, x: torch.Tensor, n_pass: int, seed: int,
             finish_layer(l, 1)
         for s, e in bounds:
             run(s, e, 5, pb, -1)
-            o.x3_head(ws.sums, ws.aff[5], 0, model.dw, model.db, 0, ws.out, e - s, 1, False)
+            _head(model, ws, n=e - s, groups=1)  # (one group: no affine stride)
             out[t, s:e].copy_(ws.out[: e - s])
     return out
 
@@ -410,55 +435,34 @@ def _forward_running(model: X3Model, x: torch.Tensor, n_pass: int, dropout: bool
                      window_offset: int, logits: bool, features: bool = False) -> torch.Tensor:
     """``features``: stop before the head and return (N, C_last) fp32 features of one model; with ``dropout``
     off this runs the per-sample-prescale layer sequence below with every mask open."""
-    spec, o = model.spec, _ops()
-    n = x.shape[0]
-    G = model.G
+    o, n, G = _ops(), x.shape[0], model.G
     if dropout and G != 1:
         raise ValueError("MC Dropout runs one model")
     if not dropout:
         n_pass = 1
     groups = n_pass if dropout else G
     ws = model.workspace(groups * n, n * G, max(groups, G))
-    thr = [rng.dropout_threshold(b.dropout) if dropout else 0 for b in spec.blocks]
-    dsc = [_dsc(b.dropout) if dropout else 1.0 for b in spec.blocks]
-    eps, mom = float(spec.bn_epsilon), float(spec.bn_momentum)
-    seed = int(seed) & ((1 << 63) - 1)
     if not dropout and not features:
-        return _predict_members(model, ws, x, G, eps, mom, logits)
+        return _predict_members(model, ws, x, G, logits)
     sl = _sign_layers()
     # BN affine of the moving statistics, per member (shared by all passes with dropout)
     for l in range(6):
-        g, b, mm, mv = model.bn[l]
-        o.x3_aff(None, g, b, mm, mv, ws.aff[l], CH[l + 1], G, CH[l + 1] if G > 1 else 0, False, 1, 1.0, eps, mom,
-                 dsc[l], ws.amax[l])
+        _aff(model, ws, l, groups=G, dropout=dropout, amax=True)
     o.x3_l1(x, model.w1, model.b1, ws.r1, None, n, G, ws.smax[0])
-    per_member = G > 1
     for l in range(1, 6):
-        src = ws.r1 if l == 1 else ws.buf[(l - 2) % 2]
-        dst = ws.sums if l == 5 else ws.buf[(l - 1) % 2]
-        wstride = model.wfrag[l].shape[1] // 8 if per_member else 0
-        sm = ws.smax_out(l, groups * n)
-        o.x3_layer(l, src, dst, model.wfrag[l], wstride, model.bias[l], model.wscale[l],
-                   CH[l + 1] if per_member else 0, ws.aff[l - 1], 2 * CH[l] if per_member else 0, None, n, groups,
-                   dropout and l == 1, thr[l - 1], thr[l], seed, int(pass_offset),
-                   int(window_offset), 0, ws.smax[l - 1], ws.amax[l - 1], sm, None, *_sign(l, sl))
+        _layer(model, ws, l, n=n, groups=groups, dropout=dropout, shared_r1=dropout, seed=seed, pass_base=pass_offset,
+               window_offset=window_offset, prescale="sample", sign=sl)
     if features:
         if groups != 1:
             raise ValueError("features of one model and one pass")
         sums = ws.sums[: n * 2 * CH[6]].view(n, 2, CH[6])
         aff = ws.aff[5][: 2 * CH[6]].view(2, CH[6])
         return (aff[0] * sums[:, 0] + aff[1] * sums[:, 1]) / 60.0
-    o.x3_head(ws.sums, ws.aff[5], 2 * CH[6] if per_member else 0, model.dw, model.db, CH[6] if per_member else 0,
-              ws.out, n, groups, bool(logits))
+    _head(model, ws, n=n, groups=groups, logits=logits)
     return ws.out[: groups * n].view(G, n_pass, n).clone()
 
 
-# ------------------------------------------------------------------------------------------------
-# CPU emulation of the engine's arithmetic from the packed fragments (fp32 conv of hi + lo weights,
-# activations split the same way): validates the packing on the CPU tier.
-# ------------------------------------------------------------------------------------------------
-def _predict_members(model: X3Model, ws: "_Workspace", x: torch.Tensor, G: int, eps: float, mom: float,
-                     logits: bool) -> torch.Tensor:
+def _predict_members(model: X3Model, ws: "_Workspace", x: torch.Tensor, G: int, logits: bool) -> torch.Tensor:
     """Deep-Ensemble predict (``uq_techniques.py:29``): BN on each member's moving statistics, every member
     in one launch per layer.  The staged activations' range-safe prescale is one power of two per member
     and block, bounded by the block output's sums of squares (max R_c <= sqrt(sum R_c^2): the moment
@@ -473,27 +477,16 @@ def _predict_members(model: X3Model, ws: "_Workspace", x: torch.Tensor, G: int, 
     effect on a probability is ~1e-7 (measured: chunked vs one launch, and against float64 at 4096
     windows, ``tests/test_x3_gpu.py::test_de_chunking_and_float64_large``); the per-sample prescale of the
     dropout path is bitwise chunk-invariant instead."""
-    spec, o = model.spec, _ops()
+    o = _ops()
     n = x.shape[0]
-    per_member = G > 1
-    ps = CH[1:] if per_member else [0] * 6
     dl = _dense_layers()
     o.zero_buffers([ws.stats[l][: G * STAT_SLOTS * 2 * CH[l + 1]] for l in range(5)])
-    g, b, mm, mv = model.bn[5]  # block 6 feeds the fp32 head: no prescale
-    o.x3_aff(None, g, b, mm, mv, ws.aff[5], CH[6], G, ps[5], False, 1, 1.0, eps, mom, 1.0, None)
+    _aff(model, ws, 5, groups=G, dropout=False)  # block 6 feeds the fp32 head: no prescale
     o.x3_l1(x, model.w1, model.b1, ws.r1, ws.stats[0], n, G, None)
     for l in range(1, 6):
-        g, b, mm, mv = model.bn[l - 1]
-        o.x3_aff(ws.stats[l - 1], g, b, mm, mv, ws.aff[l - 1], CH[l], G, ps[l - 1], False, 1, 1.0, eps, mom, 1.0,
-                 None, ws.gscale[l - 1], True)
-        src = ws.r1 if l == 1 else ws.buf[(l - 2) % 2]
-        dst = ws.sums if l == 5 else ws.buf[(l - 1) % 2]
-        wstride = model.wfrag[l].shape[1] // 8 if per_member else 0
-        o.x3_layer(l, src, dst, model.wfrag[l], wstride, model.bias[l], model.wscale[l], ps[l],
-                   ws.aff[l - 1], 2 * CH[l] if per_member else 0, ws.stats[l] if l < 5 else None, n, G, False, 0, 0,
-                   0, 0, 0, 0, None, None, None, ws.gscale[l - 1], False, False, l in dl)
-    o.x3_head(ws.sums, ws.aff[5], 2 * CH[6] if per_member else 0, model.dw, model.db, CH[6] if per_member else 0,
-              ws.out, n, G, bool(logits))
+        _aff(model, ws, l - 1, groups=G, dropout=False, stats=ws.stats[l - 1], gscale=True, running=True)
+        _layer(model, ws, l, n=n, groups=G, dropout=False, stats=ws.stats[l] if l < 5 else None, dense=dl)
+    _head(model, ws, n=n, groups=G, logits=logits)
     return ws.out[: G * n].view(G, 1, n).clone()
 
 
@@ -522,6 +515,10 @@ def features_running(model: X3Model, x: torch.Tensor, max_samples: Optional[int]
     return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
 
+# ------------------------------------------------------------------------------------------------
+# CPU emulation of the engine's arithmetic from the packed fragments (fp32 conv of hi + lo weights,
+# activations split the same way): validates the packing on the CPU tier.
+# ------------------------------------------------------------------------------------------------
 def split_f16(a: torch.Tensor):
     hi = a.half()
     lo = (a - hi.float()).half()
