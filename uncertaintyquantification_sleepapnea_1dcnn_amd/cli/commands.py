@@ -29,6 +29,7 @@
 | analyze_discrimination | (new) ROC / PR AUC and Mann-Whitney U (apnea vs normal, wrong vs right predictions) with window or patient-cluster bootstrap CIs, and the paired comparison of two detail CSVs |
 | analyze_recalibration | (new) temperature / Platt / beta recalibration of a raw prediction dump (fit set or patient cross-fit): calibration before and after on the same resamples, and the calibrated (T, N, 1) dump for the other analyze_* commands |
 | analyze_conformal | (new) split conformal prediction sets from a detail CSV: thresholds from a fit CSV and the set code of every window, or coverage / set sizes over random calibration / test splits of the patients |
+| analyze_shift_robustness | (new) one sampler (MC Dropout, Deep Ensemble, Laplace) on degraded, re-standardised copies of the test windows: accuracy, calibration, uncertainty, detection AUROC and conformal coverage per (corruption, severity), and one figure per corruption |
 """
 from __future__ import annotations
 
@@ -687,6 +688,64 @@ def analyze_conformal(argv=None):
     print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
     if a.output_csv:
         table.to_csv(a.output_csv, index=False)
+    return table
+
+
+def analyze_shift_robustness(argv=None):
+    ap = argparse.ArgumentParser(description="Uncertainty under signal corruption: one sampler on degraded, "
+                                             "re-standardised copies of the unbalanced test windows; one row per "
+                                             "(corruption, severity) plus the clean row.")
+    _uq_common(ap)
+    ap.add_argument("--method", choices=["mcd", "de", "laplace"], default="mcd")
+    ap.add_argument("--model_path", type=str, default="./AlCNN1D_no_pool.keras")
+    ap.add_argument("--n_passes", type=int, default=50, help="MC Dropout passes / Laplace samples")
+    ap.add_argument("--bn_mode", choices=["batch", "running"], default="batch",
+                    help="batch = reference semantics: the BatchNorm statistics are those of the corrupted set")
+    ap.add_argument("--model_dir", type=str, default="./models/ensemble_cnn_no_pool", help="--method de")
+    ap.add_argument("--pattern", type=str, default="AlCNN_smote_seed{}.keras")
+    ap.add_argument("--num_members", type=int, default=5)
+    ap.add_argument("--offset", type=int, default=5, help="file index of member 0 (reference loader uses i+5)")
+    ap.add_argument("--kinds", type=str, default="all", help="comma-separated corruption kinds, or 'all'")
+    ap.add_argument("--severities", type=str, default="1,2,3,4,5")
+    ap.add_argument("--channels", type=str, default="all", help="comma-separated channel indices, or 'all'")
+    ap.add_argument("--state", type=str, default="./laplace_state.npz", help="--method laplace: the fitted posterior")
+    ap.add_argument("--conformal_state", type=str, default="",
+                    help="a ConformalPredictor .npz calibrated on clean data: adds coverage and set shares")
+    ap.add_argument("--output_plot_dir", type=str, default="./uq_plots_patient/shift_robustness")
+    ap.add_argument("--output_csv", type=str, default="./uq_results_shift/shift_robustness.csv")
+    a = ap.parse_args(argv)
+    from ..models.cnn import load_model
+    from ..uq import robustness as RB
+
+    np.random.seed(a.seed)
+    Xu, yu, pids, _, _ = _load_test(a.data_dir)
+    if a.method == "de":
+        from ..parallel.ensemble import load_ensemble
+
+        predict = RB.deep_ensemble_predictor(load_ensemble(a.model_dir, a.pattern, a.num_members, a.offset))
+    elif a.method == "laplace":
+        from ..uq.laplace import LaplaceState
+
+        predict = RB.laplace_predictor(load_model(a.model_path), LaplaceState.load(a.state), a.n_passes, a.seed)
+    else:
+        predict = RB.mc_dropout_predictor(load_model(a.model_path), a.n_passes, a.bn_mode, a.seed)
+    conformal = None
+    if a.conformal_state:
+        from ..uq.conformal import ConformalPredictor
+
+        conformal = ConformalPredictor.load(a.conformal_state)
+    kinds = RB.KINDS if a.kinds == "all" else tuple(k.strip() for k in a.kinds.split(","))
+    channels = None if a.channels == "all" else [int(c) for c in a.channels.split(",")]
+    conds = RB.shift_conditions(kinds, [int(s) for s in a.severities.split(",")], channels)
+    table = RB.evaluate_shift(predict, Xu, yu, conds, seed=a.seed, patient_ids=pids, conformal=conformal,
+                              n_bootstrap=a.n_bootstrap)
+    d = os.path.dirname(a.output_csv)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    table.to_csv(a.output_csv, index=False)
+    print(f"Saved the shift table ({len(table)} rows) to {a.output_csv}")
+    if not a.no_plots:
+        RB.plot_shift({a.method: table}, a.output_plot_dir)
     return table
 
 

@@ -78,6 +78,19 @@ __device__ __forceinline__ unsigned split_key(unsigned seed, unsigned r, unsigne
 }
 __device__ __forceinline__ unsigned split_hash(unsigned skey, unsigned u) { return mix32(skey ^ mix32(u)); }
 
+// Signal corruptions of the shift sweep (uq_shift.hip; ops/rng.py shift_key / shift_word are the same functions
+// on tensors).  The key is a function of (seed, kind, channel, global window index) and never of the severity,
+// so every severity of a kind shares its draws; a draw is a 32-bit word of (key, counter): counter
+// (t << 2) | j for word j of time step t, kShiftWindowCtr | j for word j of the whole window.
+constexpr unsigned kShiftSalt = 0x3C6EF372u, kShiftWindowCtr = 0x80000000u;
+__host__ __device__ __forceinline__ unsigned shift_base(uint64_t seed) {
+  return mix32(mix32((uint32_t)(seed & 0xFFFFFFFFu) ^ kShiftSalt) ^ (uint32_t)(seed >> 32));
+}
+__device__ __forceinline__ unsigned shift_key(unsigned base, unsigned kind, unsigned c, unsigned w) {
+  return split_hash(mix32(base ^ (((kind << 8) | c) * 0x9E3779B9u)), w);
+}
+__device__ __forceinline__ unsigned shift_word(unsigned key, unsigned ctr) { return mix32(key ^ ctr); }
+
 // 16-bit uniforms of channels (c, c+1), c even, at time step t.
 __device__ __forceinline__ uint32_t dropout_bits2(uint32_t skey, uint32_t t, uint32_t c_even) {
   return mix32(skey ^ ((t << 9) | (c_even >> 1)));

@@ -1,6 +1,6 @@
 // Host interface of the UQ reduction kernels (uq_reduce.hip, uq_calib.hip, uq_patient.hip, uq_rank.hip,
-// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_recal.hip), included by those files and by uq_bindings.cpp /
-// recal_bindings.cpp.
+// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_recal.hip, uq_shift.hip), included by those files and by
+// uq_bindings.cpp / recal_bindings.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -64,4 +64,14 @@ hipError_t launch_recal_sums(const float* probs, const unsigned char* y, const i
                              double* part, double* out, hipStream_t stream);
 hipError_t launch_recal_apply(const float* probs, const int* fold, const double* thetas, long long n, int T, int F,
                               float* out, hipStream_t stream);
+// uq_shift.hip: the K conditions of a launch travel by value (kind code, parameter p, channel bit mask)
+constexpr int kShiftMaxK = 64, kShiftMaxL = 256, kShiftMaxC = 4, kShiftKinds = 8;
+struct ShiftConds {
+  double p[kShiftMaxK];
+  unsigned char kind[kShiftMaxK];
+  unsigned char mask[kShiftMaxK];
+};
+hipError_t launch_shift_corrupt(const void* x, bool x_is_double, long long n, int L, int C, const ShiftConds& conds,
+                                int K, unsigned long long seed, unsigned long long window_offset, bool restandardize,
+                                float* out, hipStream_t stream);
 }  // namespace apneauq

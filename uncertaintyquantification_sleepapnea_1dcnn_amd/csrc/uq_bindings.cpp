@@ -1,8 +1,9 @@
 // torch.library registration of the UQ reduction kernels (uq_reduce.hip, uq_calib.hip, uq_patient.hip, uq_rank.hip,
-// uq_conformal.hip, uq_laplace.hip, uq_converge.hip), namespace torch.ops.apneauq.
+// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_shift.hip), namespace torch.ops.apneauq.
 #include "bind_util.h"
 #include "uq_api.h"
 
+#include <cmath>
 #include <tuple>
 
 namespace {
@@ -413,6 +414,51 @@ at::Tensor converge(const at::Tensor& probs, const at::Tensor& y, const at::Tens
   return out;
 }
 
+// Signal corruptions of the shift sweep (uq_shift.hip): (K, n, L, C) fp32, condition k of the windows x (n, L, C)
+// fp32 or fp64.  kinds (K,) int, params (K,) float64 and chmask (K,) int are host tensors (they travel by value
+// with the launch; ops/shift.py builds them).  Limits: C <= 4, L <= 256, K <= 64, n <= 2^27 and
+// window_offset + n <= 2^32.
+at::Tensor shift_corrupt(const at::Tensor& x, const at::Tensor& kinds, const at::Tensor& params,
+                         const at::Tensor& chmask, int64_t seed, int64_t window_offset, bool restandardize) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kDouble),
+              "shift_corrupt: x must be (n, L, C) float32 or float64 on the GPU");
+  const int64_t n = x.size(0), L = x.size(1), C = x.size(2), K = kinds.numel();
+  TORCH_CHECK(L >= 1 && L <= apneauq::kShiftMaxL, "shift_corrupt: L must be in 1..", apneauq::kShiftMaxL);
+  TORCH_CHECK(C >= 1 && C <= apneauq::kShiftMaxC, "shift_corrupt: C must be in 1..", apneauq::kShiftMaxC);
+  TORCH_CHECK(K >= 1 && K <= apneauq::kShiftMaxK, "shift_corrupt: K must be in 1..", apneauq::kShiftMaxK);
+  TORCH_CHECK(n <= (int64_t(1) << 27), "shift_corrupt: at most 2^27 windows");
+  TORCH_CHECK(window_offset >= 0 && window_offset + n <= (int64_t(1) << 32),
+              "shift_corrupt: window_offset + n must stay within 2^32");
+  TORCH_CHECK(kinds.dim() == 1 && params.dim() == 1 && chmask.dim() == 1 && params.numel() == K && chmask.numel() == K,
+              "shift_corrupt: kinds, params and chmask must be (K,)");
+  auto kk = kinds.to(at::kCPU, at::kLong).contiguous();
+  auto pp = params.to(at::kCPU, at::kDouble).contiguous();
+  auto mm = chmask.to(at::kCPU, at::kLong).contiguous();
+  apneauq::ShiftConds cd = {};
+  for (int64_t k = 0; k < K; ++k) {
+    const int64_t kind = kk.data_ptr<int64_t>()[k], mask = mm.data_ptr<int64_t>()[k];
+    const double p = pp.data_ptr<double>()[k];
+    TORCH_CHECK(kind >= 0 && kind < apneauq::kShiftKinds, "shift_corrupt: kind ", kind, " is not in 0..",
+                apneauq::kShiftKinds - 1);
+    TORCH_CHECK(mask >= 0 && mask < (int64_t(1) << C), "shift_corrupt: chmask must hold bits of channels 0..C-1");
+    TORCH_CHECK(std::isfinite(p) && p >= 0.0, "shift_corrupt: params must be finite and non-negative");
+    cd.kind[k] = (unsigned char)kind;
+    cd.mask[k] = (unsigned char)mask;
+    cd.p[k] = p;
+  }
+  auto xx = x.contiguous();
+  if (!aligned(xx, 32)) xx = xx.clone();
+  TORCH_CHECK(aligned(xx, 32), "shift_corrupt: 32-B alignment required");
+  const at::DeviceGuard guard(xx.device());
+  auto out = at::empty({K, n, L, C}, xx.options().dtype(at::kFloat));
+  if (n == 0) return out;
+  check(apneauq::launch_shift_corrupt(xx.data_ptr(), xx.scalar_type() == at::kDouble, (long long)n, (int)L, (int)C, cd,
+                                      (int)K, (unsigned long long)seed, (unsigned long long)window_offset, restandardize,
+                                      out.data_ptr<float>(), cur_stream()),
+        "shift_corrupt");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(apneauq, m) {
@@ -430,6 +476,7 @@ TORCH_LIBRARY_FRAGMENT(apneauq, m) {
   m.def("laplace_gram(Tensor phi, Tensor theta, Tensor y, int range_len, int grid) -> Tensor");
   m.def("laplace_predict(Tensor phi, Tensor mx, int T) -> (Tensor, Tensor)");
   m.def("converge(Tensor probs, Tensor y, Tensor orders, Tensor counts, int rep_groups) -> Tensor");
+  m.def("shift_corrupt(Tensor x, Tensor kinds, Tensor params, Tensor chmask, int seed, int window_offset, bool restandardize) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
@@ -447,4 +494,5 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("laplace_gram", &laplace_gram);
   m.impl("laplace_predict", &laplace_predict);
   m.impl("converge", &converge);
+  m.impl("shift_corrupt", &shift_corrupt);
 }

@@ -119,6 +119,29 @@ def split_hash2(seed: int, r, u: torch.Tensor) -> torch.Tensor:
     return split_hash(seed, r, u, SPLIT_SALT2)
 
 
+SHIFT_SALT, SHIFT_WINDOW_CTR = 0x3C6EF372, 0x80000000
+
+
+def shift_base(seed: int) -> int:
+    """Seed part of the corruption key (``csrc/common.h`` ``shift_base``), a host scalar."""
+    return mix32_int(mix32_int((seed & _M32) ^ SHIFT_SALT) ^ ((seed >> 32) & _M32))
+
+
+def shift_key(seed: int, kind: int, channel, window: torch.Tensor) -> torch.Tensor:
+    """Key of the corruption draws of (seed, kind, channel, *global* window index) (int64 tensors or ints,
+    broadcast): the one host definition of ``csrc/common.h`` ``shift_key``.  The severity is not part of it, so
+    every severity of a kind shares its draws."""
+    channel = torch.as_tensor(channel, dtype=torch.int64, device=window.device)
+    kc = _mix32_t(shift_base(seed) ^ ((((kind << 8) | channel) * GOLDEN) & _M32))
+    return _mix32_t(kc ^ _mix32_t(window))
+
+
+def shift_word(key: torch.Tensor, ctr) -> torch.Tensor:
+    """32-bit draw of a key: counter ``(t << 2) | j`` is word j of time step t, ``SHIFT_WINDOW_CTR | j`` word j of
+    the whole window (``csrc/common.h`` ``shift_word``)."""
+    return _mix32_t(key ^ ctr)
+
+
 def keep_mask_torch(key: int, samples: torch.Tensor, length: int, channels: int, rate: float) -> torch.Tensor:
     """Boolean keep-mask (len(samples), length, channels) on ``samples.device``."""
     dev = samples.device

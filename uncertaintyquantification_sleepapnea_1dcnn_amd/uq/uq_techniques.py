@@ -150,6 +150,9 @@ from .recalibration import (Recalibrator, assign_folds, cross_recalibrate, evalu
 # split conformal prediction sets from any sampler's set, and their coverage over patient splits (uq/conformal.py)
 from .conformal import (ConformalPredictor, conformal_calibrate, conformal_metrics, evaluate_conformal,  # noqa: E402,F401
                         golden_conformal_split)
+# degraded copies of the windows and the (corruption, severity) sweep of any sampler (uq/robustness.py)
+from .robustness import (ShiftCondition, corrupt_windows, deep_ensemble_predictor, evaluate_shift,  # noqa: E402,F401
+                         laplace_predictor, mc_dropout_predictor, plot_shift, shift_conditions)
 
 
 # ===================== Uncertainty Metrics =====================
