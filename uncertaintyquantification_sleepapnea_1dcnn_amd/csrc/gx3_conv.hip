@@ -18,8 +18,13 @@
 //     pre-pass over its samples), also published as the tensor maximum (atomicMax, optional);
 //   * wgrad: one power of two per operand tensor from those published maxima (the forward conv
 //     published the input's, the dgrad conv dZ's; amax_kernel covers block 1's dZ).
-// The scale puts the operand's maximum in [2^13, 2^14): hi never overflows, and an element's lo
-// only turns subnormal below 2^-25 of that maximum, far under fp32 rounding of the sums.
+// The scale puts the operand's maximum in [2^13, 2^14): hi never overflows (while the exponent is not
+// clamped at +-100: maxima in [2^-86, 2^114)).  With a = v 2^s the split leaves |a - hi - lo| <=
+// max(2^-22 |a|, 2^-25): 2^-22 relative while lo is a normal fp16, i.e. down to elements of 2^-16 of
+// that maximum; below that lo (from 2^-27, hi too) is subnormal and the residual is the absolute
+// 2^-25 2^-s <= 2^-38 of the maximum per element -- far under the fp32 rounding of a sum that holds
+// terms near the maximum, but what a window 2^-30 below its workgroup neighbours is left with is 2^-8
+// relative (tests/gx3_kernel_refs.py derives and tests/test_gx3_kernels_gpu.py measures this).
 //
 //   conv_kernel<MODE, CT, HALO, VEC>  implicit GEMM D[co][row] = sum_k A[co][k] B[k][row],
 //     k = tap * Cin + ci (dgrad: the flipped, transposed kernel, Cin <-> Cout).  A = pre-packed hi/lo
