@@ -30,6 +30,7 @@
 | analyze_recalibration | (new) temperature / Platt / beta recalibration of a raw prediction dump (fit set or patient cross-fit): calibration before and after on the same resamples, and the calibrated (T, N, 1) dump for the other analyze_* commands |
 | analyze_conformal | (new) split conformal prediction sets from a detail CSV: thresholds from a fit CSV and the set code of every window, or coverage / set sizes over random calibration / test splits of the patients |
 | analyze_shift_robustness | (new) one sampler (MC Dropout, Deep Ensemble, Laplace) on degraded, re-standardised copies of the test windows: accuracy, calibration, uncertainty, detection AUROC and conformal coverage per (corruption, severity), and one figure per corruption |
+| analyze_ensemble_members | (new) ensemble composition from one raw prediction dump: every member alone and leave-one-out, pairwise diversity, greedy pruning cross-fitted by patient against first-k and random-k, and the pruned (k, N, 1) dump for the other analyze_* commands |
 """
 from __future__ import annotations
 
@@ -746,6 +747,77 @@ def analyze_shift_robustness(argv=None):
     print(f"Saved the shift table ({len(table)} rows) to {a.output_csv}")
     if not a.no_plots:
         RB.plot_shift({a.method: table}, a.output_plot_dir)
+    return table
+
+
+def analyze_ensemble_members(argv=None):
+    ap = argparse.ArgumentParser(description="Ensemble composition from one raw prediction dump: every member alone and "
+                                             "by what the ensemble loses without it, the pairwise diversity, and greedy "
+                                             "pruning (selected on some patients, scored on the others) against the "
+                                             "first k and random k members; writes the pruned (k, N, 1) dump for the "
+                                             "other analyze_* commands.")
+    ap.add_argument("--input_csv", type=str, default="./detail_patient_DE.csv",
+                    help="per-window detail CSV, read for True_Label and Patient_ID")
+    ap.add_argument("--raw_pred", type=str, default="./de_raw_pred.npy", help="(T, N[, 1]) .npy dump of the members")
+    ap.add_argument("--loss", choices=["nll", "brier"], default="nll", help="the loss the saved selection minimises")
+    ap.add_argument("--folds", type=int, default=5, help="patient folds of the cross-fit (1: none)")
+    ap.add_argument("--k_max", type=int, default=None, help="length of the saved selection path (default T)")
+    ap.add_argument("--replacement", action="store_true", help="the saved selection may pick a member again")
+    ap.add_argument("--n_orders", type=int, default=100, help="random orders of the members behind the bands")
+    ap.add_argument("--seed", type=int, default=SEED)
+    ap.add_argument("--tolerance", type=float, default=None,
+                    help="absolute distance to the all-T loss that counts as enough (default 0.001)")
+    ap.add_argument("--output_csv", type=str, default="./ensemble_members.csv")
+    ap.add_argument("--state", type=str, default=None, help=".npz the selection is saved to")
+    ap.add_argument("--output_raw_pred", type=str, default=None, help="pruned (keep, N, 1) dump (with --keep)")
+    ap.add_argument("--keep", type=int, default=None, help="members of the pruned dump")
+    ap.add_argument("--output_dir", type=str, default="./uq_plots/members")
+    ap.add_argument("--no_plots", action="store_true")
+    a = ap.parse_args(argv)
+    import pandas as pd
+
+    from ..uq import members as MM
+
+    if bool(a.output_raw_pred) != (a.keep is not None):
+        raise ValueError("--output_raw_pred and --keep go together")
+    df = pd.read_csv(a.input_csv)
+    pred = np.load(a.raw_pred).astype(np.float32)
+    n = pred.shape[1] if pred.ndim >= 2 else pred.shape[0]
+    if n != len(df):
+        raise ValueError(f"{a.raw_pred} holds {n} windows, {a.input_csv} {len(df)}")
+    y = df["True_Label"].to_numpy()
+    pids = df["Patient_ID"].to_numpy() if "Patient_ID" in df.columns else None
+    label = os.path.splitext(os.path.basename(a.input_csv))[0]
+    dev = MM.on_device(pred)
+    tol = MM.DEFAULT_TOLERANCE if a.tolerance is None else a.tolerance
+    res, det = MM.evaluate_members(dev, y, label, patient_ids=pids, n_folds=a.folds, n_orders=a.n_orders, tolerance=tol,
+                                   random_state=a.seed, output_dir=a.output_dir, make_plots=not a.no_plots,
+                                   return_details=True)
+    tab = det["table"]
+    t_count = dev.shape[0]
+    cols = ("accuracy", "sensitivity", "specificity", "nll", "brier", "loo_nll_delta", "loo_brier_delta")
+    table = pd.DataFrame({"member": np.arange(t_count), **{k: np.resize(tab[k], t_count) for k in cols}})
+    print(f"{t_count} members, {tab['n_valid']} valid windows; ensemble NLL {res['ensemble_nll']:.6f}, Brier "
+          f"{res['ensemble_brier']:.6f}; mean disagreement {res['mean_disagreement']:.6f}, ambiguity {res['ambiguity']:.6f}")
+    print(table.to_string(index=False, float_format=lambda v: f"{v:.6f}"))
+    print(f"members_needed_nll = {res['members_needed_nll']}, members_needed_brier = {res['members_needed_brier']} "
+          f"(greedy, {'held out over ' + str(a.folds) + ' patient folds' if a.folds > 1 else 'on the selection windows'}, "
+          f"within {tol:g} of all {t_count})")
+    for path in (a.output_csv, a.state, a.output_raw_pred):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    if a.output_csv:
+        table.to_csv(a.output_csv, index=False)
+    if a.state or a.output_raw_pred:
+        sel = det["selection"][a.loss]   # the whole path without replacement is what evaluate_members selected
+        if a.replacement or a.k_max is not None:
+            sel = MM.select_members(dev, y, loss=a.loss, k_max=a.k_max, replacement=a.replacement, groups=pids,
+                                    n_folds=a.folds if t_count > 1 else 1, seed=a.seed)
+        if a.state:
+            sel.save(a.state)
+        if a.output_raw_pred:
+            np.save(a.output_raw_pred, np.asarray(sel.apply(pred, a.keep), np.float32))
+            print(f"Saved the {a.keep} members {sel.order[:a.keep].tolist()} to: {a.output_raw_pred}")
     return table
 
 

@@ -1,5 +1,5 @@
 // Host interface of the UQ reduction kernels (uq_reduce.hip, uq_calib.hip, uq_patient.hip, uq_rank.hip,
-// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_recal.hip, uq_shift.hip), included by those files and by
+// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_recal.hip, uq_shift.hip, uq_members.hip), included by those files and by
 // uq_bindings.cpp / recal_bindings.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -74,4 +74,13 @@ struct ShiftConds {
 hipError_t launch_shift_corrupt(const void* x, bool x_is_double, long long n, int L, int C, const ShiftConds& conds,
                                 int K, unsigned long long seed, unsigned long long window_offset, bool restandardize,
                                 float* out, hipStream_t stream);
+// uq_members.hip
+int member_max_t();
+int member_max_q();
+int member_max_f();
+hipError_t launch_member_pairs(const float* probs, const int* y, int t_count, int n, int grid, int slices,
+                               long long* out, long long* head, hipStream_t stream);
+hipError_t launch_member_mix(const float* probs, const int* y, const unsigned char* fold, const int* counts,
+                             int t_count, int n, int n_rows, int n_folds, int grid, long long* out,
+                             hipStream_t stream);
 }  // namespace apneauq

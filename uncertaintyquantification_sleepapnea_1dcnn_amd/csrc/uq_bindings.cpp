@@ -1,5 +1,5 @@
 // torch.library registration of the UQ reduction kernels (uq_reduce.hip, uq_calib.hip, uq_patient.hip, uq_rank.hip,
-// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_shift.hip), namespace torch.ops.apneauq.
+// uq_conformal.hip, uq_laplace.hip, uq_converge.hip, uq_shift.hip, uq_members.hip), namespace torch.ops.apneauq.
 #include "bind_util.h"
 #include "uq_api.h"
 
@@ -459,6 +459,92 @@ at::Tensor shift_corrupt(const at::Tensor& x, const at::Tensor& kinds, const at:
   return out;
 }
 
+// Ensemble composition (uq_members.hip).  Both ops take exactly what the kernels read: contiguous GPU tensors,
+// probs (T, n) float32 and y (n,) int32; nothing is converted here.  member_pairs: the symmetric (T, T, 3) int64
+// table (both correct and y = 0, both correct and y = 1, the residual Gram quantised at 2^40 per window and
+// pair) and the header (n_valid, n_y1).  Limits: T <= 128, n <= 2^22 per launch (a term is at most 2^40, so
+// every sum stays below 2^62; the front end splits larger sets and adds).  grid and slices (0: auto) only change
+// the speed.
+std::tuple<at::Tensor, at::Tensor> member_pairs(const at::Tensor& probs, const at::Tensor& y, int64_t grid,
+                                                int64_t slices) {
+  TORCH_CHECK(probs.is_cuda() && probs.scalar_type() == at::kFloat && probs.dim() == 2 && probs.is_contiguous(),
+              "member_pairs: probs must be a contiguous (T, n) float32 GPU tensor");
+  const int64_t t_count = probs.size(0), n = probs.size(1);
+  TORCH_CHECK(t_count >= 1 && t_count <= apneauq::member_max_t(), "member_pairs: T must be in 1..",
+              apneauq::member_max_t());
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 22), "member_pairs: n must be in 1..2^22");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kInt && y.dim() == 1 && y.size(0) == n && y.is_contiguous() &&
+                  y.device() == probs.device(),
+              "member_pairs: y must be a contiguous (n,) int32 tensor on the GPU of probs");
+  TORCH_CHECK(grid >= 0 && grid <= 65535, "member_pairs: grid must be in 0..65535");
+  TORCH_CHECK(slices >= 0 && slices <= 64 && (slices & (slices - 1)) == 0,
+              "member_pairs: slices must be 0 or a power of two up to 64");
+  const at::DeviceGuard guard(probs.device());
+  auto up = at::zeros({t_count, t_count, 3}, probs.options().dtype(at::kLong));
+  auto head = at::zeros({2}, probs.options().dtype(at::kLong));
+  check(apneauq::launch_member_pairs(probs.data_ptr<float>(), y.data_ptr<int>(), (int)t_count, (int)n, (int)grid,
+                                     (int)slices, reinterpret_cast<long long*>(up.data_ptr<int64_t>()),
+                                     reinterpret_cast<long long*>(head.data_ptr<int64_t>()), cur_stream()),
+        "member_pairs");
+  // the kernel writes a <= b and the strict lower triangle stays zero, so the mirror is one add
+  auto planes = up.permute({2, 0, 1});   // (3, T, T)
+  auto full = planes + at::triu(planes, 1).transpose(1, 2);
+  return std::make_tuple(full.permute({1, 2, 0}).contiguous(), head);
+}
+
+// member_mix: (F, Q, 7) int64 sums per fold and per row of integer member counts: n_valid, n_y1, nll_q (2^36),
+// brier_q (2^40), correct, true_pos, pred_pos of the mixture sum_t c_t p_t / k.  fold (n,) uint8 is optional
+// (absent: one fold); a window with a code >= F contributes to nothing.  Limits: T <= 128, Q <= 64, F <= 16,
+// n <= 2^21 per launch (an nll term stays below 2^41), counts (a host tensor) in 0..255 with a positive row sum.
+at::Tensor member_mix(const at::Tensor& probs, const at::Tensor& y, const c10::optional<at::Tensor>& fold,
+                      const at::Tensor& counts, int64_t n_folds, int64_t grid) {
+  TORCH_CHECK(probs.is_cuda() && probs.scalar_type() == at::kFloat && probs.dim() == 2 && probs.is_contiguous(),
+              "member_mix: probs must be a contiguous (T, n) float32 GPU tensor");
+  const int64_t t_count = probs.size(0), n = probs.size(1);
+  TORCH_CHECK(t_count >= 1 && t_count <= apneauq::member_max_t(), "member_mix: T must be in 1..",
+              apneauq::member_max_t());
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 21), "member_mix: n must be in 1..2^21");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kInt && y.dim() == 1 && y.size(0) == n && y.is_contiguous() &&
+                  y.device() == probs.device(),
+              "member_mix: y must be a contiguous (n,) int32 tensor on the GPU of probs");
+  TORCH_CHECK(n_folds >= 1 && n_folds <= apneauq::member_max_f(), "member_mix: F must be in 1..",
+              apneauq::member_max_f());
+  const unsigned char* fp = nullptr;
+  if (fold.has_value()) {
+    TORCH_CHECK(fold->is_cuda() && fold->scalar_type() == at::kByte && fold->dim() == 1 && fold->size(0) == n &&
+                    fold->is_contiguous() && fold->device() == probs.device(),
+                "member_mix: fold must be a contiguous (n,) uint8 tensor on the GPU of probs");
+    fp = fold->data_ptr<uint8_t>();
+  }
+  TORCH_CHECK(counts.is_cpu() && counts.scalar_type() == at::kInt && counts.dim() == 2 && counts.size(1) == t_count &&
+                  counts.is_contiguous(),
+              "member_mix: counts must be a contiguous (Q, T) int32 host tensor");
+  const int64_t n_rows = counts.size(0);
+  TORCH_CHECK(n_rows >= 1 && n_rows <= apneauq::member_max_q(), "member_mix: Q must be in 1..",
+              apneauq::member_max_q());
+  TORCH_CHECK(grid >= 0 && grid <= 65535, "member_mix: grid must be in 0..65535");
+  // the counts are a host tensor (as the conditions of shift_corrupt are): their values are checked here without a
+  // device synchronise, and they are uploaded with the launch
+  const int* cp = counts.data_ptr<int>();
+  for (int64_t q = 0; q < n_rows; ++q) {
+    int64_t k = 0;
+    for (int64_t t = 0; t < t_count; ++t) {
+      const int c = cp[q * t_count + t];
+      TORCH_CHECK(c >= 0 && c <= 255, "member_mix: counts must lie in 0..255");
+      k += c;
+    }
+    TORCH_CHECK(k >= 1, "member_mix: every row of counts needs a positive sum");
+  }
+  const at::DeviceGuard guard(probs.device());
+  auto dev_counts = counts.to(probs.device(), /*non_blocking=*/true);
+  auto out = at::zeros({n_folds, n_rows, 7}, probs.options().dtype(at::kLong));
+  check(apneauq::launch_member_mix(probs.data_ptr<float>(), y.data_ptr<int>(), fp, dev_counts.data_ptr<int>(), (int)t_count,
+                                   (int)n, (int)n_rows, (int)n_folds, (int)grid,
+                                   reinterpret_cast<long long*>(out.data_ptr<int64_t>()), cur_stream()),
+        "member_mix");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(apneauq, m) {
@@ -477,6 +563,8 @@ TORCH_LIBRARY_FRAGMENT(apneauq, m) {
   m.def("laplace_predict(Tensor phi, Tensor mx, int T) -> (Tensor, Tensor)");
   m.def("converge(Tensor probs, Tensor y, Tensor orders, Tensor counts, int rep_groups) -> Tensor");
   m.def("shift_corrupt(Tensor x, Tensor kinds, Tensor params, Tensor chmask, int seed, int window_offset, bool restandardize) -> Tensor");
+  m.def("member_pairs(Tensor probs, Tensor y, int grid, int slices) -> (Tensor, Tensor)");
+  m.def("member_mix(Tensor probs, Tensor y, Tensor? fold, Tensor counts, int n_folds, int grid) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
@@ -495,4 +583,6 @@ TORCH_LIBRARY_IMPL(apneauq, CUDA, m) {
   m.impl("laplace_predict", &laplace_predict);
   m.impl("converge", &converge);
   m.impl("shift_corrupt", &shift_corrupt);
+  m.impl("member_pairs", &member_pairs);
+  m.impl("member_mix", &member_mix);
 }

@@ -153,6 +153,9 @@ from .conformal import (ConformalPredictor, conformal_calibrate, conformal_metri
 # degraded copies of the windows and the (corruption, severity) sweep of any sampler (uq/robustness.py)
 from .robustness import (ShiftCondition, corrupt_windows, deep_ensemble_predictor, evaluate_shift,  # noqa: E402,F401
                          laplace_predictor, mc_dropout_predictor, plot_shift, shift_conditions)
+# ensemble composition: member diversity, leave-one-out effects and greedy pruning of a prediction set (uq/members.py)
+from .members import (MemberSelection, evaluate_members, member_diversity, member_pairs, member_table,  # noqa: E402,F401
+                      select_members, subset_brier)
 
 
 # ===================== Uncertainty Metrics =====================
