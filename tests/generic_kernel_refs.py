@@ -12,17 +12,59 @@ float64 -- so what is left between kernel and reference is fp32 accumulation, a 
   does not round to nearest;
 * ``UB = 2^-8`` for one bf16 store: the unit roundoff of its 8-bit significand (round to nearest).
 """
+import atexit
+import functools
+import json
 import math
+import os
+import shutil
+import subprocess
+import tempfile
 
 import numpy as np
 import torch
 
+from uncertaintyquantification_sleepapnea_1dcnn_amd.csrc import build
 from uncertaintyquantification_sleepapnea_1dcnn_amd.ops import rng
 
 U32 = 2.0 ** -23
 UB = 2.0 ** -8
 EPS = float(np.float32(1e-3))          # the kernels take eps / momentum as float
 MOMENTUM = float(np.float32(0.99))
+
+
+# ------------------------------------------------------------------------------------------ launch geometry
+# Stated once, in csrc/generic_geo.h.  The tests learn it by running the stand-alone host program
+# tests/generic_geo_check.cpp (which also checks the header against brute force, test_generic_geo_cpu.py),
+# built once per session into a temporary directory.
+BF16, GF32 = 0, 1                  # generic_geo.h Engine
+INFER, TRAIN, LINEAR = 0, 1, 2     # ... and Mode
+
+
+@functools.lru_cache(maxsize=None)
+def geo_check_exe(name="generic_geo_check", flags=()):
+    """tests/<name>.cpp built with the host compiler against csrc/ (once per session)."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    tmp = tempfile.mkdtemp(prefix=name + "_")
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+    exe = os.path.join(tmp, name)
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", f"-I{build.HERE}", *flags,
+                        os.path.join(os.path.dirname(os.path.abspath(__file__)), name + ".cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+@functools.lru_cache(maxsize=None)
+def geo_table(what, *args):
+    """One launch's plan (``--table``).  ``"conv", engine, mode, n, L, cin, cout, k, pool, in_rs`` -> kind
+    ("staged" = conv_lds_kernel, "vec", "elem"), ct, nct, grid, span, lds_rows, lds_stride, lds_bytes,
+    nc, ...; ``"wgrad", R, cin, cout, k, part_floats`` (gf32) -> groups, rpg, grid;
+    ``"gt_wgrad", R, cin, cout, k, det, part_floats`` -> ok, im2col, nco, kmax, rgs, ...; ``"const"``."""
+    r = subprocess.run([geo_check_exe(), "--table", what, *map(str, args)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return json.loads(r.stdout)
 
 
 def f64(t):
@@ -352,17 +394,6 @@ WGRAD_CASES = [
     (36, 11, 20, 9, 45),    # KMAX 15 (k = 11); nco 1; R = 495
     (96, 15, 256, 9, 30),   # KMAX 15 (k = 15); nco 2; R = 396
 ]
-
-
-def wgrad_nco(k, cout):
-    """The co tiles per wave ``launch_gt_wgrad`` picks (csrc/generic_wgrad.hip)."""
-    tiles = (cout + 15) // 16
-    nmax = 4 if k <= 5 else 3 if k <= 9 else 2
-    nco = 1
-    for c in range(2, nmax + 1):
-        if -(-tiles // (4 * c)) * 4 * c <= -(-tiles // (4 * nco)) * 4 * nco:
-            nco = c
-    return nco
 
 
 def wgrad_fixture(cin, k, cout, n, L):

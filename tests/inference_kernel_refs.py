@@ -40,6 +40,8 @@ import torch.nn.functional as F
 from uncertaintyquantification_sleepapnea_1dcnn_amd.models.spec import BlockSpec, ModelSpec
 from uncertaintyquantification_sleepapnea_1dcnn_amd.ops import fused, rng
 
+from . import generic_kernel_refs as GK
+
 U32 = 2.0 ** -23
 UB = 2.0 ** -8
 BN_EPS = 2.0 ** -10
@@ -427,11 +429,10 @@ def conv_cases():
 
 
 def conv_kernel_of(c):
-    """Which kernel ``launch_generic_conv`` picks (its own rule)."""
-    span = 128 + 2 * ((c["k"] - 1) // 2)
-    if c["cin"] % 8 == 0 and span * (2 * c["cin"] + 16) <= 80 * 1024:
-        return "conv_lds_kernel"
-    return "conv_block_kernel<true>" if c["cin"] % 8 == 0 else "conv_block_kernel<false>"
+    """Which kernel ``launch_generic_conv`` picks: the plan of csrc/generic_geo.h (inference: in_rs = L)."""
+    L, cpad = c.get("L", 30), (c.get("cout", 16) + 15) // 16 * 16
+    kind = GK.geo_table("conv", GK.BF16, GK.INFER, c.get("n", 1), L, c["cin"], cpad, c["k"], int(c.get("pool", False)), L)["kind"]
+    return {"staged": "conv_lds_kernel", "vec": "conv_block_kernel<true>", "elem": "conv_block_kernel<false>"}[kind]
 
 
 def conv_fixture(c, idx):

@@ -291,22 +291,23 @@ def test_elementwise_allowances_and_pool_exclusions(bf16, C, n, L):
 
 
 def test_case_tables_reach_every_path():
-    """The dispatch decisions the case comments name, recomputed from the launchers' rules."""
-    nco = {(cin, k, cout): G.wgrad_nco(k, cout) for cin, k, cout, _, _ in G.WGRAD_CASES}
+    """The dispatch decisions the case comments name, read from the launch plans (csrc/generic_geo.h)."""
+    wg = {(cin, k, cout): G.geo_table("gt_wgrad", n * (L + k - 1), cin, cout, k, 0, 0) for cin, k, cout, n, L in G.WGRAD_CASES}
+    nco = {c: t["nco"] for c, t in wg.items()}
     assert set(nco.values()) == {1, 2, 3, 4}
     assert nco[96, 5, 256] == 4 and nco[224, 9, 192] == 3 and nco[100, 9, 256] == 2 and nco[96, 15, 256] == 2
-    kmax = {3 if k <= 3 else 5 if k <= 5 else 9 if k <= 9 else 15 for cin, k, _, _, _ in G.WGRAD_CASES if cin * k > 32}
-    assert kmax == {3, 5, 9, 15} and any(cin * k <= 32 for cin, k, _, _, _ in G.WGRAD_CASES)
+    assert [nco[c[:3]] for c in G.WGRAD_CASES] == [1, 1, 2, 2, 1, 1, 4, 3, 2, 1, 2]      # as the case comments say
+    assert {t["kmax"] for t in wg.values() if not t["im2col"]} == {3, 5, 9, 15}
+    assert [c[:3] for c in G.WGRAD_CASES if wg[c[:3]]["im2col"]] == [(1, 7, 12), (3, 9, 20), (4, 7, 100)]
+    assert wg[36, 3, 100]["rgs"] == 3 and wg[36, 3, 100]["chunks"] == 9 and wg[1, 7, 12]["rgs"] == 1
 
-    def conv_path(cin, L, k, n):   # launch_generic_conv (mode 1: in_rs = L + 2 p)
-        p = (k - 1) // 2
-        span = 128 + -(-127 // L) * 2 * p + 2 * p
-        if cin % 8 == 0 and span * (2 * cin + 16) <= 80 * 1024:
-            return "lds"
-        return "vector" if cin % 8 == 0 else "element"
-
-    paths = [conv_path(cin, L, k, n) for cin, L, k, _, n in G.CONV_CASES]
-    assert paths == ["lds"] * 5 + ["vector"] * 2 + ["element"] * 4
+    plans = [G.geo_table("conv", G.BF16, G.TRAIN, n, L, cin, (cout + 15) // 16 * 16, k, 0, L + k - 1)
+             for cin, L, k, cout, n in G.CONV_CASES]     # gt_conv mode 1: in_rs = L + 2 p
+    assert [p["kind"] for p in plans] == ["staged"] * 5 + ["vec"] * 2 + ["elem"] * 4
+    # "70.5 KB of LDS (just under the 80 KB limit)", "LDS span 97.5 KB", "LDS span 462 KB"
+    assert plans[2]["lds_bytes"] == 70528 and plans[2]["lds_limit_bytes"] == 80 * 1024
+    assert [p["span"] * p["lds_stride"] / 1024 for p in plans[5:7]] == [97.5, 462.0]
+    assert [p["grid"][1] for p in plans] == [1, 1, 1, 1, 1, 1, 1, 2, 2, 1, 1]
     assert sum((cout + 15) // 16 > 8 for _, _, _, cout, _ in G.CONV_CASES) == 2   # second channel block
     # packed slot sum from 256 slots; the one-slot tail joins the previous range
     assert [s for s in G.BN_NSLOTS if s >= 256 and s % 64 == 1] == [257, 321, 385]

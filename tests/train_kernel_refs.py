@@ -15,14 +15,10 @@ boundary is the allowance of exactly the output entries reading that element wid
 ``|w|``.  Everything is computed in torch float64 on the device of its inputs; ``rnd=False`` switches every
 internal rounding off (the composed step then equals float64 autograd, see the CPU tests).
 """
-import atexit
 import functools
 import json
 import math
-import os
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import torch
@@ -47,19 +43,8 @@ OMM = 1.0 - MOMENTUM                         # 1.f - momentum is exact in fp32 a
 # Stated once, in csrc/train_geo.h.  The tests learn it by running the stand-alone host program
 # tests/train_geo_check.cpp (which also checks the header against brute force, test_train_geo_cpu.py): built
 # once per session into a temporary directory, with the wgrad table csrc/build.py would build the kernels with.
-@functools.lru_cache(maxsize=None)
 def geo_check_exe():
-    cxx = shutil.which("g++") or shutil.which("c++")
-    assert cxx, "no host C++ compiler"
-    tmp = tempfile.mkdtemp(prefix="train_geo_")
-    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
-    exe = os.path.join(tmp, "train_geo_check")
-    table = [d for d in build.EXTRA if d.startswith("-DAPNEAUQ_WG_TABLE=")]
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", f"-I{build.HERE}", *table,
-                        os.path.join(os.path.dirname(os.path.abspath(__file__)), "train_geo_check.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return G.geo_check_exe("train_geo_check", tuple(d for d in build.EXTRA if d.startswith("-DAPNEAUQ_WG_TABLE=")))
 
 
 @functools.lru_cache(maxsize=None)

@@ -24,8 +24,7 @@
 
 #include "common.h"
 #include "generic_api.h"
-
-#include <type_traits>
+#include "generic_geo.h"
 
 namespace apneauq {
 namespace generic {
@@ -44,7 +43,7 @@ struct ConvArgs {
   unsigned long long seed;
   int in_rs, in_off;      // input row addressing: sample n, step t at row n * in_rs + in_off + t
   float* stats;           // kTrain: BN moment sums (kStatSlots, 2, Cout); deterministic mode: (2 grid.x, 2, Cout),
-                          // one slot per (workgroup, wave row) written with plain stores
+                          // one slot per (workgroup, wave row) written with plain stores (generic_geo.h)
   int det;
   long long x_rows;       // rows of the input buffer (staging bound)
   int lds_rows, lds_stride;  // conv_lds_kernel: staged rows, bytes per LDS row
@@ -53,10 +52,9 @@ struct ConvArgs {
 // Epilogue modes: kInfer = bias + ReLU + BN(running) [+ pool] [+ dropout] (the folded epi rows);
 // kTrain = relu(acc + bias) stored as the pre-BN activation z, with the per-channel BN moments
 // (sum, sum of squares) accumulated into kStatSlots interleaved copies; kLinear = acc as is (dgrad).
-enum { kInfer = 0, kTrain = 1, kLinear = 2 };
-constexpr int kStatSlots = 16;
+using ggeo::kInfer, ggeo::kTrain, ggeo::kLinear, ggeo::kStatSlots;
 
-constexpr int kRT = 4, kCT = 4;  // row / channel tiles per wave; a workgroup is 2 x 2 waves
+constexpr int kRT = ggeo::kRT, kCT = 4;  // row / channel tiles per wave; a workgroup is 2 x 2 waves
 
 // Epilogue of one wave: acc[c][r] holds rows (rn[r], rt[r]) x channels ct*16 + 4h .. +3 per lane.
 template <int MODE>
@@ -381,6 +379,8 @@ hipError_t launch_generic_conv(const void* x, const void* wfrag, const float* ep
                                int n_win, unsigned pass_offset, unsigned window_offset, unsigned long long seed,
                                hipStream_t stream, int mode, int in_rs, int in_off, float* stats, long long x_rows,
                                int det_slots) {
+  const ggeo::ConvPlan P = ggeo::conv_plan(ggeo::kBf16, mode, n, L, cin, cout_pad, ksize, pool, in_rs, x_rows > 0);
+  if (P.rows == 0) return hipSuccess;
   generic::ConvArgs A;
   A.x = reinterpret_cast<const __bf16*>(x);
   A.wfrag = reinterpret_cast<const bf16x8*>(wfrag);
@@ -388,47 +388,34 @@ hipError_t launch_generic_conv(const void* x, const void* wfrag, const float* ep
   A.y = reinterpret_cast<__bf16*>(y);
   A.n = n;
   A.L = L;
-  A.pool = pool;
-  A.Lp = pool ? (L + 1) / 2 * 2 : L;
+  A.pool = P.pool;
+  A.Lp = P.Lp;
   A.cin = cin;
   A.cout = cout;
   A.cout_pad = cout_pad;
   A.ksize = ksize;
-  A.nstep = (ksize * cin + 31) / 32;
-  A.lout = pool ? L / 2 : L;
-  A.dropout = dropout;
+  A.nstep = P.nstep;
+  A.lout = P.lout;
+  A.dropout = mode == generic::kInfer ? dropout : 0;
   A.thr = thr;
   A.layer = layer;
   A.n_win = n_win;
   A.pass_offset = pass_offset;
   A.window_offset = window_offset;
   A.seed = seed;
-  A.in_rs = in_rs > 0 ? in_rs : L;
+  A.in_rs = P.in_rs;
   A.in_off = in_off;
   A.stats = stats;
-  if (mode != generic::kInfer) {
-    A.pool = 0;
-    A.Lp = L;
-    A.lout = L;
-    A.dropout = 0;
-  }
-  const long long rows = (long long)n * A.Lp;
-  if (rows == 0) return hipSuccess;
-  constexpr int kRowsWG = 2 * generic::kRT * 16, kChWG = 2 * generic::kCT;  // 128 rows x 8 channel tiles
-  const dim3 grid((unsigned)((rows + kRowsWG - 1) / kRowsWG), (unsigned)((cout_pad / 16 + kChWG - 1) / kChWG));
   A.det = mode == generic::kTrain && det_slots > 0;
-  if (A.det && (long long)grid.x * 2 > det_slots) return hipErrorInvalidValue;  // one slot per (workgroup, wave row)
-  // LDS staging when every row a workgroup can touch fits: 128 output rows span at most
-  // 127 + ceil(127 / Lp) * max(0, in_rs - Lp) input rows, plus the 2 * pad halo
-  const long long extra = (long long)(127 + A.Lp - 1) / A.Lp * (A.in_rs > A.Lp ? A.in_rs - A.Lp : 0);
-  const long long span = 128 + extra + 2 * (long long)((ksize - 1) / 2);
-  const int stride = 2 * cin + 16;
   A.x_rows = x_rows;
-  A.lds_rows = (int)span;
-  A.lds_stride = stride;
-  const bool use_lds = cin % 8 == 0 && span * stride <= 80 * 1024 && x_rows > 0;
-  if (use_lds) {
-    const size_t lds = (size_t)span * stride;
+  A.lds_rows = P.lds_rows;
+  A.lds_stride = P.lds_stride;
+  if (A.det && P.det_slots > det_slots) return hipErrorInvalidValue;  // one slot per (workgroup, wave row)
+  const dim3 grid((unsigned)P.grid_x, (unsigned)P.grid_y);
+  // LDS staging when every row a workgroup can touch fits (P.span).  (The order of the instantiations
+  // below is the order of the kernels in the code object.)
+  if (P.kind == ggeo::kStaged) {
+    const size_t lds = (size_t)P.lds_bytes;
     if (mode == generic::kTrain)
       hipLaunchKernelGGL(generic::conv_lds_kernel<generic::kTrain>, grid, dim3(256), lds, stream, A);
     else if (mode == generic::kLinear)
@@ -440,7 +427,7 @@ hipError_t launch_generic_conv(const void* x, const void* wfrag, const float* ep
   // direct-gather kernel: channel counts that are not a multiple of 8, or rows beyond the LDS span
   auto gather = [&](auto mode_c) {
     constexpr int M = decltype(mode_c)::value;
-    if (cin % 8 == 0)
+    if (P.kind == ggeo::kVec)
       hipLaunchKernelGGL((generic::conv_block_kernel<true, M>), grid, dim3(256), 0, stream, A);
     else
       hipLaunchKernelGGL((generic::conv_block_kernel<false, M>), grid, dim3(256), 0, stream, A);

@@ -25,14 +25,15 @@
 
 #include "common.h"
 #include "generic_api.h"
+#include "generic_geo.h"
 
 namespace apneauq {
 namespace gwgrad {
 
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 
-constexpr int kThreads = 256;
-constexpr int kChunk = 64;  // rows staged per step (two 32-row k-steps)
+using ggeo::kThreads;
+using ggeo::kChunk;  // rows staged per step (two 32-row k-steps)
 
 __host__ __device__ constexpr int odd32(int bytes) { return ((bytes + 31) / 32) % 2 ? (bytes + 31) / 32 * 32 : (bytes + 31) / 32 * 32 + 32; }
 
@@ -426,19 +427,17 @@ static void wg_go(const gwgrad::WgArgs& A, int grid, hipStream_t st) {
 }
 
 template <int NCO>
-static hipError_t wg_dispatch(const gwgrad::WgArgs& A, int grid, bool im2col, hipStream_t st) {
-  if (im2col) {
+static hipError_t wg_dispatch(const gwgrad::WgArgs& A, int grid, const ggeo::GtWgradPlan& P, hipStream_t st) {
+  if (P.im2col) {
     wg_go<NCO, 1, true>(A, grid, st);
-  } else if (A.k <= 3) {
+  } else if (P.kmax == 3) {
     wg_go<NCO, 3, false>(A, grid, st);
-  } else if (A.k <= 5) {
+  } else if (P.kmax == 5) {
     wg_go<NCO, 5, false>(A, grid, st);
-  } else if (A.k <= 9) {
+  } else if (P.kmax == 9) {
     wg_go<NCO, 9, false>(A, grid, st);
-  } else if (A.k <= 15) {
-    wg_go<NCO, 15, false>(A, grid, st);
   } else {
-    return hipErrorInvalidValue;
+    wg_go<NCO, 15, false>(A, grid, st);
   }
   return hipGetLastError();
 }
@@ -462,8 +461,10 @@ hipError_t launch_ordered_sum(const float* part, int nrows, long long ncols, flo
 hipError_t launch_gt_wgrad(const void* x, long long x_rows, const void* dz, long long R, int cin, int cout, int k,
                            float* gw, hipStream_t st, float* part, long long part_floats) {
   if (R <= 0) return hipSuccess;
-  if (k < 1 || k > 15 || cin < 1 || cout < 1) return hipErrorInvalidValue;
+  if (k < 1 || k > ggeo::kWgKMax || cin < 1 || cout < 1) return hipErrorInvalidValue;
   if (x_rows < R + k - 1) return hipErrorInvalidValue;  // every tap's rows must exist
+  const ggeo::GtWgradPlan P = ggeo::gt_wgrad_plan(R, cin, cout, k, part != nullptr, part_floats);
+  if (!P.ok) return hipErrorInvalidValue;
   gwgrad::WgArgs A;
   A.x = reinterpret_cast<const __bf16*>(x);
   A.dz = reinterpret_cast<const __bf16*>(dz);
@@ -474,46 +475,18 @@ hipError_t launch_gt_wgrad(const void* x, long long x_rows, const void* dz, long
   A.cout = cout;
   A.k = k;
   A.part = part;
-  const bool im2col = cin * k <= 32;
-  // co tiles per wave: the fewest padded tile slots (4 waves x NCO per block), then the largest NCO; the
-  // accumulators (k x NCO tiles) are capped so a workgroup keeps >= 2 waves per SIMD
-  const int co_tiles = (cout + 15) / 16;
-  const int nmax = k <= 5 ? 4 : k <= 9 ? 3 : 2;
-  int nco = 1;
-  for (int c = 2; c <= nmax; ++c) {
-    const int slots_c = (co_tiles + 4 * c - 1) / (4 * c) * 4 * c, slots_b = (co_tiles + 4 * nco - 1) / (4 * nco) * 4 * nco;
-    if (slots_c <= slots_b) nco = c;
-  }
-  A.n_ci = im2col ? 1 : (cin + 15) / 16;
-  A.n_co = (co_tiles + 4 * nco - 1) / (4 * nco);
-  const long long chunks = (R + gwgrad::kChunk - 1) / gwgrad::kChunk;
-  // ~2048 workgroups (8 per CU over the 256 CUs), but at least minc chunks each: every workgroup ends
-  // with k * 16 * 64 * NCO fp32 atomics, and the chip adds ~1.3 TB/s of atomic bytes, so at 4 chunks
-  // per workgroup the k = 9 blocks of ModelSpec(30, 1) spent ~100 us of a ~106 us wgrad on them.
-  const long long minc = k <= 3 ? 4 : 2 * k;
-  const long long blocks = (long long)A.n_ci * A.n_co;
-  long long rg = 2048 / blocks;
-  if (rg < 1) rg = 1;
-  if (rg > (chunks + minc - 1) / minc) rg = (chunks + minc - 1) / minc;
-  const long long wfl = (long long)k * cin * cout;
-  if (part != nullptr && rg > part_floats / wfl) rg = part_floats / wfl;  // one partial slice per row group
-  if (rg < 1) rg = 1;
-  A.chunks_per_wg = (int)((chunks + rg - 1) / rg);
-  rg = (chunks + A.chunks_per_wg - 1) / A.chunks_per_wg;
-  const long long grid = blocks * rg;
-  if (grid > 0x7FFFFFFF) return hipErrorInvalidValue;
-  if (part != nullptr && rg * wfl > part_floats) return hipErrorInvalidValue;
+  A.n_ci = P.n_ci;
+  A.n_co = P.n_co;
+  A.chunks_per_wg = P.chunks_per_wg;
   hipError_t e;
-  switch (nco) {
-    case 1: e = wg_dispatch<1>(A, (int)grid, im2col, st); break;
-    case 2: e = wg_dispatch<2>(A, (int)grid, im2col, st); break;
-    case 3: e = wg_dispatch<3>(A, (int)grid, im2col, st); break;
-    default: e = wg_dispatch<4>(A, (int)grid, im2col, st); break;
+  switch (P.nco) {
+    case 1: e = wg_dispatch<1>(A, (int)P.grid, P, st); break;
+    case 2: e = wg_dispatch<2>(A, (int)P.grid, P, st); break;
+    case 3: e = wg_dispatch<3>(A, (int)P.grid, P, st); break;
+    default: e = wg_dispatch<4>(A, (int)P.grid, P, st); break;
   }
   if (e != hipSuccess || part == nullptr) return e;
-  gwgrad::RedDst d = {};
-  d.seg[0] = {gw, wfl};
-  return ordered_reduce(part, (int)rg, wfl, d, st);
+  return launch_ordered_sum(part, (int)P.rgs, P.wfl, gw, st);
 }
 
 // part (deterministic mode, nullable): ceil(n / 4) * (C + 2) floats of per-workgroup records.
@@ -566,15 +539,14 @@ hipError_t launch_gt_pack(int nb, const float* const* w, void* const* fwd, void*
     B.k = k[i];
     B.cin = cin[i];
     B.cout = cout[i];
-    B.nf = (long long)((k[i] * cin[i] + 31) / 32) * 512 * ((cout[i] + 15) / 16);
-    B.nd = (long long)((k[i] * cout[i] + 31) / 32) * 512 * ((cin[i] + 15) / 16);
+    B.nf = ggeo::frag_elems(k[i], cin[i], cout[i]);
+    B.nd = ggeo::frag_elems(k[i], cout[i], cin[i]);
     const long long t = B.nf + (B.dgr ? B.nd : 0);
     most = t > most ? t : most;
   }
   for (int i = 0; i < nz; ++i) most = std::max(most, zw[i] / 4);
-  long long gx = (most + 255) / 256;
-  if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(gwgrad::pack_kernel, dim3((unsigned)gx, nb + nz), dim3(256), 0, st, P);
+  const unsigned gx = (unsigned)ggeo::pack_grid(most);
+  hipLaunchKernelGGL(gwgrad::pack_kernel, dim3(gx, nb + nz), dim3(256), 0, st, P);
   return hipGetLastError();
 }
 

@@ -19,14 +19,15 @@
 //                      ordered reduce of generic_wgrad.hip: deterministic weight gradients.
 #include "common.h"
 #include "generic_api.h"
+#include "generic_geo.h"
 
 namespace apneauq {
 
 namespace gf32 {
 
-constexpr int kRT = 4;  // per wave: 4 row tiles x CT channel tiles (conv_kernel template)
-constexpr int kStatSlots = 16;   // atomic-mode moment slots (== generic::kStatSlots)
-enum { kTrain = 1, kLinear = 2 };
+using ggeo::kRT;  // per wave: 4 row tiles x CT channel tiles (conv_kernel template)
+using ggeo::kStatSlots;  // atomic-mode moment slots
+using ggeo::kTrain, ggeo::kLinear;
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -237,7 +238,8 @@ struct WgArgs {
 // on disjoint bank quarters.
 // K (taps) is a template parameter: the accumulators of every tap stay in registers (a runtime tap
 // count indexed them through scratch memory).
-constexpr int kWgRC = 64, kWgKMax = 15, kWgXS = 48, kWgDS = 80;
+using ggeo::kWgRC, ggeo::kWgKMax;
+constexpr int kWgXS = 48, kWgDS = 80;
 template <int K>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgArgs A) {
   constexpr int XR = kWgRC + K - 1;                 // X rows of a chunk (with the tap halo)
@@ -328,28 +330,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgArgs A) {
     }
 }
 
-// dispatch the runtime tap count (1 .. kWgKMax) to its wgrad_kernel<K> instantiation
-template <int K>
-bool launch_wgrad_k(int k, dim3 grid, const WgArgs& A, hipStream_t st) {
-  if (k == K) {
-    hipLaunchKernelGGL(wgrad_kernel<K>, grid, dim3(256), 0, st, A);
-    return true;
-  }
-  if constexpr (K < kWgKMax) return launch_wgrad_k<K + 1>(k, grid, A, st);
-  return false;
-}
-
 }  // namespace gf32
 
 hipError_t launch_gf32_conv(const float* x, const float* w, const float* bias, float* y, float* stats, int n, int L,
                             int cin, int cout, int ksize, int mode, int in_rs, int in_off, int flip, int det_slots,
                             hipStream_t st) {
   gf32::ConvArgs A{x, w, bias, y, stats, n, L, cin, cout, ksize, in_rs, in_off, flip, det_slots > 0 ? 1 : 0};
-  const long long rows = (long long)n * L;
-  if (rows == 0) return hipSuccess;
-  const int nct = (cout + 15) / 16, ct = nct % 6 == 0 ? 3 : 4;
-  const dim3 grid((unsigned)((rows + 127) / 128), (unsigned)((nct + 2 * ct - 1) / (2 * ct)));
-  if (mode == gf32::kTrain && A.det && (long long)grid.x * 2 > det_slots) return hipErrorInvalidValue;
+  const ggeo::ConvPlan P = ggeo::conv_plan(ggeo::kGf32, mode, n, L, cin, cout, ksize, 0, in_rs, true);
+  if (P.rows == 0) return hipSuccess;
+  const int ct = P.ct;
+  const dim3 grid((unsigned)P.grid_x, (unsigned)P.grid_y);
+  if (mode == gf32::kTrain && A.det && P.det_slots > det_slots) return hipErrorInvalidValue;
   if (mode == gf32::kTrain && ct == 3)
     hipLaunchKernelGGL((gf32::conv_kernel<gf32::kTrain, 3>), grid, dim3(256), 0, st, A);
   else if (mode == gf32::kTrain)
@@ -365,25 +356,18 @@ hipError_t launch_gf32_conv(const float* x, const float* w, const float* bias, f
 hipError_t launch_gf32_wgrad(const float* x, const float* dz, long long R, int cin, int cout, int k, float* gw,
                              float* part, long long part_floats, hipStream_t st) {
   if (R <= 0) return hipSuccess;
-  if (k < 1 || k > 15) return hipErrorInvalidValue;
-  const long long wfl = (long long)k * cin * cout;
-  long long groups = part_floats / wfl;
-  const long long ci_t = (cin + 31) / 32, co_g = (cout + 63) / 64;
-  // ~2 workgroups per CU in total (71 KB of LDS each), at least 256 rows per group
-  long long want = (512 + ci_t * co_g - 1) / (ci_t * co_g);
-  if (want > (R + 255) / 256) want = (R + 255) / 256;
-  if (groups > want) groups = want;
-  if (groups > 65535) groups = 65535;
-  if (groups < 1) return hipErrorInvalidValue;
-  long long rpg = (R + groups - 1) / groups;
-  rpg = (rpg + gf32::kWgRC - 1) / gf32::kWgRC * gf32::kWgRC;  // whole LDS row chunks
-  groups = (R + rpg - 1) / rpg;
-  gf32::WgArgs A{x, dz, part, R, cin, cout, k, (int)rpg};
-  const dim3 grid((unsigned)ci_t, (unsigned)co_g, (unsigned)groups);
-  if (!gf32::launch_wgrad_k<1>(k, grid, A, st)) return hipErrorInvalidValue;
+  if (k < 1 || k > gf32::kWgKMax) return hipErrorInvalidValue;
+  const ggeo::RowGroups G = ggeo::wgrad_row_groups(R, cin, cout, k, part_floats);  // (71 KB of LDS per workgroup)
+  if (G.groups < 1) return hipErrorInvalidValue;
+  gf32::WgArgs A{x, dz, part, R, cin, cout, k, (int)G.rpg};
+  const dim3 grid((unsigned)G.ci_t, (unsigned)G.co_g, (unsigned)G.groups);
+  const bool ok = ggeo::dispatch_k<1, gf32::kWgKMax>(k, [&](auto K) {
+    hipLaunchKernelGGL(gf32::wgrad_kernel<decltype(K)::value>, grid, dim3(256), 0, st, A);
+  });
+  if (!ok) return hipErrorInvalidValue;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return launch_ordered_sum(part, (int)groups, wfl, gw, st);
+  return launch_ordered_sum(part, (int)G.groups, G.wfl, gw, st);
 }
 
 }  // namespace apneauq
